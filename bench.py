@@ -19,8 +19,16 @@ scaling), each rank runs the step on its shard and the partial tables are merged
 One JSON line on rank 0: metric/value/unit/... plus
   "roofline":     dominant kernel's algorithmic bytes per launch / its HIP-event duration,
                   against the 8 TB/s HBM3E peak (guide: ~6.3 TB/s is the copy ceiling)
+
+A plain run only sets up, warms up, times the --steps steps and prints that line.  --full adds
+what takes runs of its own:
+  "roofline.measured_ceiling" / "scheme_ceiling": this GPU's HBM read and copy rates, measured
+                  here (a 1 B-row COUNT(*) scan and a 4 GB device copy)
   "cpu_baseline": the oracle (CPU restatement of HeavyDB's CPU executor; kind "port") timed on
-                  this box's host cores on a bounded sample of the same workload.
+                  this box's host cores on a bounded sample of the same workload
+  "per_rank":     N > 1: one more, untimed step taken apart on every rank (step, then merge)
+
+--dump-outputs DIR writes the rows the last timed step returned as DIR/*.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -70,7 +78,14 @@ def parse_args():
                     help="TEST ONLY (tests/test_bench_multi_rank.py): every rank runs the host simulation of the library "
                          "(tests/hostsim) on CPU tensors and gloo carries the collectives — exercises the N-rank control flow "
                          "of this script without a GPU; its numbers are not measurements")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the HBM ceiling, the CPU baseline and (N > 1) the per-rank breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows the last timed step returned as DIR/*.npy (float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
+    return args
 
 
 def _free_port() -> int:
@@ -215,6 +230,42 @@ def _keyed_merge_path():
     return multi_gpu.LAST_KEYED_PATH or None
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(shard, out_dir: str, prefix: str = "", budget_bytes: int = DUMP_BUDGET_BYTES) -> None:
+    """The rows a caller of the step receives (ResultSet.fetch), as float64 .npy files that two builds can be compared by:
+      target<t>.npy    one column per target, SQL NULL as NaN (integers are exact up to 2^53)
+      row_index.npy    which rows these are: the rows are sorted by their target values (target 0 first), so that builds
+                       that lay the table out differently agree row for row; past the budget, a fixed seeded sample
+      row_count.npy    the number of rows, target_sums.npy: per target, the sum over every row (NULLs left out)
+    Floating-point aggregates are summed in no fixed order on the device: from run to run they agree to a few ulps, not
+    bit for bit, so compare them with a tolerance."""
+    import numpy as np
+    rs = shard.result_set()
+    q = rs.getQueryMemDesc()
+    ival, dval, nul = rs.fetch()
+    n, nt = ival.shape
+    raw = [dval[:, t] if q.target_is_fp[t] else ival[:, t] for t in range(nt)]
+    order = np.lexsort(raw[::-1]) if n else np.zeros(0, dtype=np.int64)
+    cols = []
+    for t in range(nt):
+        c = raw[t][order].astype(np.float64)
+        c[nul[order, t] != 0] = np.nan
+        cols.append(c)
+    keep = max((budget_bytes - (1 << 20)) // (8 * (nt + 1)), 1)
+    idx = np.arange(n)
+    if n > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for t, c in enumerate(cols):
+        np.save(os.path.join(out_dir, f"{prefix}target{t}.npy"), c[idx])
+    np.save(os.path.join(out_dir, f"{prefix}row_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{prefix}row_count.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, f"{prefix}target_sums.npy"), np.array([np.nansum(c) for c in cols], dtype=np.float64))
+
+
 def main():
     args = parse_args()
     import torch
@@ -266,7 +317,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         total_rows = int(t.item())
 
-    ceiling = measure_ceiling(torch, local_rank) if rank == 0 and not args.hostsim else None
+    ceiling = measure_ceiling(torch, local_rank) if args.full and rank == 0 and not args.hostsim else None
 
     prepart = bool(args.prepartitioned and cfg in ("cfg3", "cfg3f") and world > 1)
     extra = {"prepartitioned": True} if prepart else {}
@@ -325,10 +376,14 @@ def main():
     ms_per_step = elapsed * 1e3 / max(args.steps, 1)
     rows_per_s = total_rows * args.steps / elapsed
 
+    if args.dump_outputs:
+        dump_outputs(last[0], args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "",
+                     budget_bytes=DUMP_BUDGET_BYTES // world)
+
     # N > 1: one more, UNTIMED step taken apart on every rank — the rank's own step, then the merge — so that the line
     # shows where a rank's time goes (the timed loop above has no sync between the two)
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         from heavydb_amd import multi_gpu
         sync()
         t1 = time.perf_counter()
@@ -397,7 +452,8 @@ def main():
     if args.verify and rank == 0:
         rs = last[0].result_set()
         ival, dval, nul = rs.fetch()
-        verify = {"groups": int(ival.shape[0])}
+        # timed_steps / launches: counted by the timed loop itself (its reports), not echoed from --steps
+        verify = {"groups": int(ival.shape[0]), "timed_steps": len(reports), "launches": int(sum(r.n_launches for r in reports))}
         if cfg in ("cfg3", "cfg3f"):
             verify["sum_count"] = int(ival[:, 1].sum())
         if cfg == "cfg4":
@@ -448,7 +504,7 @@ def main():
         out["data"] = "HOST SIMULATION (tests/hostsim + gloo): control flow only, not a measurement"
     if verify:
         out["verify"] = verify
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.hostsim:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.hostsim:
         try:
             out["cpu_baseline"] = cpu_baseline(cfg, info, args.cpu_seconds, int(args.cpu_rows))
         except Exception as e:  # the baseline is a report, never a reason to lose the bench line

@@ -23,7 +23,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" "
 done
 cat $out/cfg3f_pmc.txt | cut -c1-170
 for cfg in cfg1 cfg2 cfg3 cfg4; do
-  timeout 600 python bench.py --config $cfg --steps 3 --warmup 1 --verify > $out/bench_$cfg.log 2>&1
+  timeout 600 python bench.py --full --config $cfg --steps 3 --warmup 1 --verify > $out/bench_$cfg.log 2>&1
   grep '"metric"' $out/bench_$cfg.log | cut -c1-1600
 done
 rm -rf $out/trace

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 bash tools/gpu_round_profiles.sh r02
 out=gpurun_out/round_r02
-timeout 900 python bench.py > $out/bench_cfg3f.log 2>&1
+timeout 900 python bench.py --full > $out/bench_cfg3f.log 2>&1
 grep '"metric"' $out/bench_cfg3f.log | cut -c1-300
 for extra in "--sum-dim" "--sparse" "--sparse --sum-dim"; do
   tag=$(echo "cfg4$extra" | tr -d ' ' | tr -- '-' '_')

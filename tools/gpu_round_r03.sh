@@ -10,7 +10,7 @@ mkdir -p $out
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
 python -c "import torch; x=torch.zeros(4).cuda(); print('device ok', x.sum().item())" || { echo "no GPU"; exit 3; }
 timeout 1200 python -u -m pytest tests -m gpu -q -p no:cacheprovider --durations=12 -rf > $out/pytest_gpu.log 2>&1; echo "pytest exit $?"; tail -3 $out/pytest_gpu.log
-timeout 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench exit $?"
+timeout 300 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench exit $?"
 timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $out/trace -o cfg3f -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline > $out/bench_rocprof.json 2> $out/bench_rocprof.err
 find $out/trace -name "*kernel_stats.csv" -exec cp {} $out/cfg3f_kernel_stats.csv \; ; rm -rf $out/trace
 for grp in FETCH_SIZE WRITE_SIZE; do

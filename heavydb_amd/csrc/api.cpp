@@ -1,5 +1,6 @@
-// api.cpp — the C-ABI of libmi355q (include/mi355q.h): host C++ that turns a plan into a
-// launch sequence over the HIP kernel family.  No torch, no JIT, no CUDA-compat layer.
+// api.cpp — the C-ABI entry points of libmi355q (include/mi355q.h) and the step executor: host C++ that turns a plan
+// into a launch sequence over the HIP kernel family (execute_impl: the route order, the plain step, its finish and the
+// asynchronous tail).  The derived-plan routes it asks first live in api_routes.cpp.  No torch, no JIT, no CUDA-compat layer.
 //
 // Shape of one call, against the reference's step executor (heavyai/heavydb):
 //   mi355q_execute ~ Executor::executeWorkUnit (Execute.cpp:2144) after fetchChunks:
@@ -267,352 +268,10 @@ int64_t mi355q_qmd_slot_col_offset(const mi355q_qmd* qmd, int32_t s) {
 
 }  // extern "C"
 
-extern "C" {
-
-// ------------------------------------------------------------------------------- packed keys
-// Baseline-hash GROUP BY over several columns whose ranges together fit 62 bits: pack the key
-// columns of every row into one int64 column (one streaming pass), run the step on that column
-// with the single-key fast family (partition-then-aggregate), and re-emit the finished table
-// with the real key components — MurmurHash3 over the key bytes, the reference's layout.  The
-// slots of a row are the same in both tables (key projections take no slot in the baseline
-// layout), so the re-emission copies them.  Anything this cannot take (no ranges, too many
-// bits, joins, small inputs) stays with the row kernel.
 namespace {
 
-constexpr int32_t kNotTaken = INT32_MIN + 7;  // internal: "use the ordinary path"
-constexpr int64_t kIdxPartMinRows = (int64_t)8 << 20;  // below this the row kernel / LDS members are as good
 constexpr int32_t kRetryNoIdx = INT32_MIN + 9;  // internal: the index-partitioned family gave up (spill list), plan again without it
 constexpr int32_t kRetryNoLds = INT32_MIN + 8;  // internal: the LDS group-by ran out of replica room, plan again without it
-
-bool pack_spec_of(const mi355q_plan& p, const mi355q_qmd& q, const DevPlan& d, PackSpec* ps) {
-  if (p.join_outer_col >= 0 || p.n_group_cols < 1 || d.col0_key_quirk) return false;
-  std::memset(ps, 0, sizeof(*ps));
-  ps->n = p.n_group_cols;
-  // ONE plain FLOAT key on a baseline table: the table stores the double it widens to, so the "packed" column is that
-  // double's bit pattern and the single-key families (which read 8-byte keys) take the step — the reference
-  // benchmark's GROUP BY cast(x AS FLOAT) (MultiStep/MSBS001-005)
-  if (p.n_group_cols == 1 && q.desc_type == MI355Q_GROUP_BY_BASELINE_HASH && p.cols[p.group_cols[0]].type == MI355Q_FLOAT &&
-      p.cols[p.group_cols[0]].encoding == MI355Q_ENC_NONE && q.key_width == 8) {
-    ps->raw_f32 = 1;
-    ps->cols[0] = p.group_cols[0];
-    ps->types[0] = d.group_types[0];
-    return true;
-  }
-  for (int g = 0; g < p.n_group_cols; ++g)  // other floating-point keys have no integer range to pack
-    if (type_is_fp(p.cols[p.group_cols[g]].type) || type_is_f32(p.cols[p.group_cols[g]].type)) return false;
-  if (q.desc_type == MI355Q_GROUP_BY_PERFECT_HASH) {
-    // single-column tables that fit LDS already have their kernel; multi-column ones reach it
-    // through the packed index (mode 2); bucketed keys cannot be restored from their index
-    const bool small = q.entry_count * (int64_t)q.row_size <= 64 * 1024;
-    // one plain NOT NULL INT / BIGINT (or FIXED(32)) key: k_perfect_lds reads it natively.  Every other
-    // single key — dictionary ids, FIXED(8/16), DATE in days, nullable (translated) keys — reaches the
-    // same kernel through the index column the pack kernel decodes it into.
-    if (small && p.n_group_cols < 2) {
-      const mi355q_col_desc& kc = p.cols[p.group_cols[0]];
-      const int tc = d.group_types[0];
-      const bool native = !kc.nullable && !q.group_bucket[0] &&
-                          (tc == MI355Q_INT32 || tc == MI355Q_INT64 ||
-                           (tc_enc(tc) == MI355Q_ENC_FIXED && tc_storage(tc) == MI355Q_INT32));
-      if (native) return false;
-    }
-    if (q.entry_count >= ((int64_t)1 << 31)) return false;
-    ps->mode = small ? 2 : 1;
-    for (int g = 0; g < p.n_group_cols; ++g) {
-      // a bucketed range maps (key - min) / bucket to the index: the key can only be restored from the
-      // index when every value is a multiple of the bucket above min — DATE in days decoded to seconds
-      if (q.group_bucket[g] &&
-          !(tc_enc(d.group_types[g]) == MI355Q_ENC_DATE_IN_DAYS && q.group_bucket[g] == 86400 && q.group_min[g] % 86400 == 0))
-        return false;
-      ps->bucket[g] = q.group_bucket[g];
-      ps->cols[g] = p.group_cols[g];
-      ps->types[g] = d.group_types[g];
-      ps->translate[g] = d.group_translate[g];
-      ps->min[g] = q.group_min[g];
-      ps->card[g] = (uint64_t)q.group_card[g];
-      ps->mul[g] = d.group_mul[g];
-      ps->null_key[g] = q.group_null_key[g];
-    }
-    return true;
-  }
-  // baseline layouts: several key columns, or ONE key column whose table has 4-byte key components
-  // (pick_baseline_key_width: every key fits int32 — the reference benchmark's x10k_s10k / x100k_s10k BIGINT keys):
-  // the partitioned family emits 8-byte keys, so the step runs on the packed (key - min) column into a temporary
-  // 8-byte-key table and k_unpack_emit lays the finished groups out with the real 4-byte components
-  if (q.desc_type != MI355Q_GROUP_BY_BASELINE_HASH) return false;
-  if (p.n_group_cols < 2 && q.key_width != 4) return false;
-  int shift = 0;
-  for (int g = 0; g < p.n_group_cols; ++g) {
-    const int c = p.group_cols[g];
-    const mi355q_range& r = p.col_ranges[c];
-    if (!r.valid || r.min > r.max) return false;
-    const __int128 span = (__int128)r.max - (__int128)r.min + 1 + (p.cols[c].nullable ? 1 : 0);
-    if (span > ((__int128)1 << 61)) return false;
-    int bits = 1;
-    while (((__int128)1 << bits) < span) ++bits;
-    if (shift + bits > 62) return false;  // the packed key must stay below EMPTY_KEY_64
-    ps->cols[g] = c;
-    ps->types[g] = d.group_types[g];
-    ps->nullable[g] = p.cols[c].nullable != 0;
-    ps->shift[g] = shift;
-    ps->min[g] = r.min;
-    ps->card[g] = (uint64_t)span;
-    ps->mask[g] = (((uint64_t)1) << bits) - 1;
-    shift += bits;
-  }
-  return true;
-}
-
-int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options* opts, mi355q_result** out,
-                     mi355q_exec_report* report, mi355q_pending** pend, int64_t* reserved);
-
-int32_t execute_packed_multi(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
-                             const mi355q_qmd& q, const DevPlan& d, int n_cus, mi355q_result** out,
-                             mi355q_exec_report* report, int64_t* reserved) {
-  PackSpec ps;
-  // kernel_variant 1 = "the row kernel / direct members", as everywhere else
-  if (o.kernel_variant == 1) return kNotTaken;
-  if (!pack_spec_of(*plan, q, d, &ps)) return kNotTaken;
-  const int nf = in->n_frags, nc = plan->n_cols;
-  int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
-  // small inputs: the row kernel is as fast (kernel_variant 2 asks for this path regardless, 1 for
-  // the row kernel)
-  if (o.kernel_variant == 1 || (o.kernel_variant != 2 && total_rows < ((int64_t)8 << 20))) return kNotTaken;
-
-  // derived plan: the packed column (appended, range unknown -> baseline, 8-byte key) is the
-  // only group column; key projections are dropped (they own no slot)
-  mi355q_plan p2 = *plan;
-  // where the packed column sits in the derived step's column table: appended — or, when the table is full
-  // (MI355Q_MAX_COLS), in the place of a key column nothing else reads (its only reader, the grouping, is what the packed
-  // column replaces; key projections own no slot in the derived plan)
-  int pk = nc;
-  if (nc >= MI355Q_MAX_COLS) {
-    pk = -1;
-    for (int g = 0; g < plan->n_group_cols && pk < 0; ++g) {
-      const int c = plan->group_cols[g];
-      bool used = false;
-      for (int t = 0; t < plan->n_targets; ++t) {
-        const mi355q_target& tg = plan->targets[t];
-        if (tg.agg == MI355Q_PROJECT_KEY) continue;
-        used = used || (tg.table == 0 && tg.col == c) ||
-               ((tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF) && tg.cond.col == c);
-      }
-      for (int k = 0; k < plan->n_quals; ++k) used = used || plan->quals[k].col == c;
-      if (!used) pk = c;
-    }
-    if (pk < 0) return kNotTaken;
-  }
-  const int nc2 = pk == nc ? nc + 1 : nc;
-  p2.n_cols = nc2;
-  p2.cols[pk] = mi355q_col_desc{MI355Q_INT64, 0, MI355Q_ENC_NONE, 0};
-  p2.col_ranges[pk] = mi355q_range{};
-  p2.n_group_cols = 1;
-  p2.group_cols[0] = pk;
-  p2.n_targets = 0;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    if (plan->targets[t].agg != MI355Q_PROJECT_KEY) p2.targets[p2.n_targets++] = plan->targets[t];
-  }
-  if (p2.n_targets == 0) return kNotTaken;
-  if (ps.mode == 1) {  // a baseline table at 50 % fill for the groups of the perfect layout
-    const int64_t guess = 2 * q.entry_count;
-    if (guess > (int64_t)UINT32_MAX) return kNotTaken;
-    p2.max_groups_buffer_entry_guess = guess;
-  }
-  if (ps.mode == 2) {  // the index is a perfect-hash key itself: range [0, entries)
-    p2.col_ranges[pk].valid = 1;
-    p2.col_ranges[pk].min = 0;
-    p2.col_ranges[pk].max = q.entry_count - 1;
-  }
-  // the temporary table always has 8-byte slots: k_unpack_emit / k_unpack_perfect read it quad by
-  // quad, and a multi-pass run reduces it with 64-bit adds (pick_target_compact_width would narrow a
-  // COUNT(*)-only derived plan to 4-byte slots)
-  p2.bigint_count = 1;
-  mi355q_qmd q2;
-  if (qmd_init(p2, &q2) != MI355Q_OK) return kNotTaken;
-  if (q2.slot_width != 8 || q2.row_size % 8 != 0) return kNotTaken;
-  if (ps.mode == 2) {
-    if (q2.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || q2.entry_count != q.entry_count) return kNotTaken;
-    ps.tmp_idx_target = q2.idx_target_as_key;
-    ps.tmp_init = q2.keyless ? q2.init_vals[q2.idx_target_as_key] : 0;
-  } else if (q2.desc_type != MI355Q_GROUP_BY_BASELINE_HASH) {
-    return kNotTaken;
-  }
-  if (ps.mode == 0 && (q2.slot_count != q.slot_count || q2.entry_count != q.entry_count)) return kNotTaken;
-  // where every slot of the final row comes from: a slot of the packed step's row, or (perfect
-  // layouts: projected keys own a slot) the original value of a key component
-  {
-    int t2 = 0;
-    for (int i = 0; i < MI355Q_MAX_SLOTS; ++i) ps.slot_src[i] = 0;
-    for (int t = 0; t < plan->n_targets; ++t) {
-      const int sf = q.target_slot[t];
-      if (plan->targets[t].agg == MI355Q_PROJECT_KEY) {
-        if (sf >= 0) ps.slot_src[sf] = -(1 + q.target_key_idx[t]);
-        continue;
-      }
-      const int st = q2.target_slot[t2++];
-      const int ns = plan->targets[t].agg == MI355Q_AVG ? 2 : 1;
-      for (int j = 0; j < ns; ++j) {
-        if (sf < 0 || st < 0 || q2.init_vals[st + j] != q.init_vals[sf + j]) return kNotTaken;
-        ps.slot_src[sf + j] = st + j;
-      }
-    }
-  }
-
-  if (reserved) {  // RESERVE / explain: the derived single-key step over all fragments (one pass), nothing launched
-    route_note(ps.raw_f32 ? "k_pack_keys (FLOAT key widened)" : ps.mode == 0 ? "k_pack_keys (bit-packed key)" : ps.mode == 1 ? "k_pack_keys (entry index, baseline temp)"
-                                                                             : "k_pack_keys (entry index, perfect temp)");
-    std::vector<const void*> cols2((size_t)nf * nc2, nullptr);
-    for (int i = 0; i < nf; ++i)
-      for (int c = 0; c < nc; ++c)
-        if (c != pk) cols2[(size_t)i * nc2 + c] = in->col_buffers[(size_t)i * nc + c];
-    mi355q_inputs in2 = *in;
-    in2.col_buffers = cols2.data();
-    mi355q_exec_options o2 = o;
-    o2.out_buffer = nullptr;
-    const int32_t e2 = execute_impl(&p2, &in2, &o2, out, report, nullptr, reserved);
-    if (e2 == MI355Q_OK) route_note(ps.mode == 2 ? "k_unpack_perfect" : "k_unpack_emit");
-    return e2;
-  }
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  // memory: two temporary tables + the packed column of one pass (a group of fragments)
-  const int64_t tmp_bytes = (q2.entry_count * (int64_t)q2.row_size + 255) & ~255ll;
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  int64_t pack_budget = std::min<int64_t>((int64_t)16 << 30, ((int64_t)free_b + ctx.aux_bytes) / 3);
-  int64_t pass_rows = pack_budget / 8;
-  if (o.pass_rows > 0 && o.pass_rows < pass_rows)  // tests: force several passes
-    pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);
-  if (pass_rows < max_frag_rows + 2 * (int64_t)nf) return kNotTaken;
-  if (pass_rows > total_rows) pass_rows = total_rows;
-  const int64_t pack_bytes = ((pass_rows + 2 * (int64_t)nf) * 8 + 255) & ~255ll;
-  const int64_t tab_bytes = sizeof(void*) * (size_t)nf;
-  const int64_t need = pack_bytes + 2 * tmp_bytes + ((tab_bytes + 255) & ~255ll) + 256;
-  if (ctx.aux_bytes < need) {
-    if (ctx.aux) (void)hipFree(ctx.aux);
-    ctx.aux = nullptr;
-    ctx.aux_bytes = 0;
-    if (hipMalloc(&ctx.aux, (size_t)need) != hipSuccess) {
-      (void)hipGetLastError();
-      return kNotTaken;
-    }
-    ctx.aux_bytes = need;
-  }
-  char* aux = (char*)ctx.aux;
-  int64_t* packed = (int64_t*)aux;
-  int64_t* tmp_a = (int64_t*)(aux + pack_bytes);
-  int64_t* tmp_b = (int64_t*)(aux + pack_bytes + tmp_bytes);
-  int64_t** d_packed_tab = (int64_t**)(aux + pack_bytes + 2 * tmp_bytes);
-  int32_t* d_err = (int32_t*)(aux + pack_bytes + 2 * tmp_bytes + ((tab_bytes + 255) & ~255ll));
-
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { mi355q_result_free(r); }
-  } rg{res};
-  // device copy of the caller's column table (the pack kernel reads the key columns from it)
-  DevWord d_tab, d_rows;
-  HIP_TRY(hipMalloc(&d_tab.p, sizeof(void*) * (size_t)std::max(1, nf * nc)));
-  HIP_TRY(hipMalloc(&d_rows.p, sizeof(int64_t) * (size_t)std::max(1, nf)));
-  HIP_TRY(hipMemcpyAsync(d_tab.p, in->col_buffers, sizeof(void*) * (size_t)(nf * nc), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d_rows.p, in->num_rows, sizeof(int64_t) * (size_t)nf, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(d_err, 0, 64, s));
-
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-
-  std::vector<const void*> cols2((size_t)nf * nc2);
-  std::vector<int64_t*> h_packed((size_t)nf);
-  mi355q_exec_report acc{};
-  int pass = 0;
-  int f = 0;
-  while (f < nf) {
-    int f1 = f;
-    int64_t rows = 0, off = 0;
-    while (f1 < nf && (f1 == f || rows + in->num_rows[f1] <= pass_rows)) {
-      h_packed[f1] = packed + off;
-      off += (in->num_rows[f1] + 1) & ~(int64_t)1;  // 16-byte aligned fragment chunks
-      rows += in->num_rows[f1];
-      ++f1;
-    }
-    const int pnf = f1 - f;
-    HIP_TRY(hipMemcpyAsync(d_packed_tab, h_packed.data() + f, sizeof(void*) * (size_t)pnf, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_pack_keys(ps, (const int8_t* const*)d_tab.p + (size_t)f * nc, (const int64_t*)d_rows.p + f, pnf,
-                             nc, max_frag_rows, d_packed_tab, d_err, n_cus, s));
-    for (int i = 0; i < pnf; ++i) {
-      for (int c = 0; c < nc; ++c) cols2[(size_t)i * nc2 + c] = in->col_buffers[(size_t)(f + i) * nc + c];
-      cols2[(size_t)i * nc2 + pk] = h_packed[f + i];
-    }
-    mi355q_inputs in2 = *in;
-    in2.n_frags = pnf;
-    in2.col_buffers = cols2.data();
-    in2.num_rows = in->num_rows + f;
-    mi355q_exec_options o2 = o;
-    o2.stream = s;
-    o2.out_buffer = pass == 0 ? tmp_a : tmp_b;
-    mi355q_result* r2 = nullptr;
-    mi355q_exec_report rep2{};
-    const int32_t e2 = mi355q_execute(&p2, &in2, &o2, &r2, &rep2);
-    if (e2 == MI355Q_ERR_OUT_OF_GPU_MEM || e2 == MI355Q_ERR_UNSUPPORTED) return kNotTaken;
-    if (e2) return e2;  // incl. < 0: out of slots -> the caller grows the table
-    struct R2Guard {
-      mi355q_result* r;
-      ~R2Guard() { if (r) mi355q_result_free(r); }
-    } r2g{r2};
-    if (pass > 0) {
-      HIP_TRY(launch_reduce(r2->dplan, q2.idx_target_as_key, tmp_a, tmp_b, q2.entry_count, d_err, s));
-    }
-    if (pass == 0) {  // the report names the member the first (a full-sized) pass ran
-      std::snprintf(acc.kernel_name, sizeof(acc.kernel_name), "%s", rep2.kernel_name);
-      acc.variant = rep2.variant;
-    }
-    acc.kernel_ms += rep2.kernel_ms;
-    acc.n_launches += rep2.n_launches;
-    acc.spilled_rows += rep2.spilled_rows;
-    f = f1;
-    ++pass;
-  }
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  if (nf > 0)
-    HIP_TRY(launch_unpack_emit(ps, d, tmp_a, q2.entry_count, q2.row_size / 8, q2.key_bytes / 8, res->buf, d_err, s));
-  if (ev1) HIP_TRY(hipEventRecord(ev1, s));
-  int32_t h_err = 0;
-  HIP_TRY(hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_err == MI355Q_ERR_UNSUPPORTED) return kNotTaken;  // a key outside its declared range
-  if (h_err) return h_err;
-  if (report) {
-    *report = acc;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  rg.r = nullptr;
-  *out = res;
-  return MI355Q_OK;
-}
-
 
 // ---------------------------------------------------------------------------------------------------
 // The part of a step that needs the host to look at the device: error words, the spill counter, the
@@ -766,1529 +425,9 @@ void drain_inflight(DeviceCtx& ctx) {
   }
 }
 
-// reserved != nullptr: RESERVE mode — plan the step, size and allocate the per-device workspace it would use,
-// launch nothing (mi355q_reserve_workspace); the column pointers are not looked at
-int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options* opts,
-                     mi355q_result** out, mi355q_exec_report* report, mi355q_pending** pend,
-                     int64_t* reserved = nullptr);
-
-// Grouped steps whose aggregates read SEVERAL value columns, over inputs large enough for the partitioned / packed
-// routes: one run per value column through the single-value families, zipped into the final layout
-// (kernels_generic.hip k_zip_targets).  kNotTaken when the shape does not call for it.
-int32_t execute_multi_value(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
-                            const mi355q_qmd& q, const DevPlan& d, mi355q_result** out, mi355q_exec_report* report,
-                            int64_t* reserved) {
-  if (plan->n_group_cols < 1 || plan->join_outer_col >= 0 || q.slot_width != 8 || q.output_columnar || d.col0_key_quirk)
-    return kNotTaken;
-  // the value columns, in order of first use
-  int vcols[MI355Q_MAX_TARGETS], n_v = 0;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const mi355q_target& tg = plan->targets[t];
-    if (tg.agg == MI355Q_PROJECT_KEY || tg.col < 0) continue;
-    if (tg.table != 0 || tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF) return kNotTaken;
-    bool seen = false;
-    for (int k = 0; k < n_v; ++k) seen = seen || vcols[k] == tg.col;
-    if (!seen) vcols[n_v++] = tg.col;
-  }
-  if (n_v < 2 || n_v > 4) return kNotTaken;
-  int64_t total_rows = 0;
-  for (int f = 0; f < in->n_frags; ++f) total_rows += in->num_rows[f];
-  // small inputs: one pass of the row kernel is as good (kernel_variant 2 = "the large-input members", as for the
-  // packed route: how the tests reach this route with small tables)
-  if (o.kernel_variant != 2 && total_rows < ((int64_t)8 << 20)) return kNotTaken;
-
-  if (reserved) {  // RESERVE / explain: the run over the first value column (every run has the same shape)
-    char note[64];
-    std::snprintf(note, sizeof(note), "%d runs (one per value column) + k_zip_targets, each", n_v);
-    route_note(note);
-    mi355q_plan sp = *plan;
-    sp.n_targets = 0;
-    for (int t = 0; t < plan->n_targets; ++t) {
-      const mi355q_target& tg = plan->targets[t];
-      if (tg.agg == MI355Q_PROJECT_KEY || tg.col < 0 || tg.col == vcols[0]) sp.targets[sp.n_targets++] = tg;
-    }
-    mi355q_exec_options o2 = o;
-    o2.out_buffer = nullptr;
-    return execute_impl(&sp, in, &o2, out, report, nullptr, reserved);
-  }
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  // the final table starts EMPTY (result_create_impl only allocates): k_zip_targets claims its keys with CAS
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  DevWord err;
-  HIP_TRY(hipMalloc(&err.p, 64));
-  HIP_TRY(hipMemsetAsync(err.p, 0, 64, s));
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-  mi355q_exec_report acc{};
-  for (int k = 0; k < n_v; ++k) {
-    // run k: the targets over value column k; run 0 also carries COUNT(*) and the key projections
-    mi355q_plan sp = *plan;
-    sp.n_targets = 0;
-    int orig_of[MI355Q_MAX_TARGETS];
-    for (int t = 0; t < plan->n_targets; ++t) {
-      const mi355q_target& tg = plan->targets[t];
-      const bool valueless = tg.agg == MI355Q_PROJECT_KEY || tg.col < 0;
-      if (valueless ? k == 0 : tg.col == vcols[k]) {
-        orig_of[sp.n_targets] = t;
-        sp.targets[sp.n_targets++] = tg;
-      }
-    }
-    mi355q_exec_options o2 = o;
-    o2.stream = s;
-    o2.out_buffer = nullptr;
-    mi355q_result* r2 = nullptr;
-    mi355q_exec_report rep2{};
-    if (int32_t e2 = mi355q_execute(&sp, in, &o2, &r2, &rep2)) return e2;
-    struct R2Guard {
-      mi355q_result* r;
-      ~R2Guard() { if (r) mi355q_result_free(r); }
-    } r2g{r2};
-    const mi355q_qmd& q2 = r2->qmd;
-    if (q2.desc_type != q.desc_type || q2.entry_count != q.entry_count || q2.slot_width != 8 || q2.output_columnar ||
-        (q.desc_type == MI355Q_GROUP_BY_BASELINE_HASH && q2.key_width != q.key_width))
-      return MI355Q_ERR_UNSUPPORTED;
-    int32_t src[MI355Q_MAX_SLOTS], dst[MI355Q_MAX_SLOTS];
-    int n = 0;
-    for (int t2 = 0; t2 < sp.n_targets; ++t2) {
-      const int t = orig_of[t2];
-      const int ss = q2.target_slot[t2], sf = q.target_slot[t];
-      if ((ss < 0) != (sf < 0)) return MI355Q_ERR_UNSUPPORTED;   // (a projection read from the key columns on both sides)
-      if (ss < 0) continue;
-      const int ns = plan->targets[t].agg == MI355Q_AVG ? 2 : 1;
-      for (int j = 0; j < ns; ++j) {
-        if (q2.init_vals[ss + j] != q.init_vals[sf + j]) return MI355Q_ERR_UNSUPPORTED;
-        src[n] = ss + j;
-        dst[n] = sf + j;
-        ++n;
-      }
-    }
-    HIP_TRY(launch_zip_targets(res->dplan, r2->dplan, q2.idx_target_as_key, r2->buf, res->buf, src, dst, n, (int32_t*)err.p, s));
-    HIP_TRY(hipStreamSynchronize(s));   // r2 is freed at the end of this iteration
-    if (k == 0) {
-      std::snprintf(acc.kernel_name, sizeof(acc.kernel_name), "%s", rep2.kernel_name);
-      acc.variant = rep2.variant;
-    }
-    acc.kernel_ms += rep2.kernel_ms;
-    acc.n_launches += rep2.n_launches;
-    acc.spilled_rows += rep2.spilled_rows;
-  }
-  if (ev1) HIP_TRY(hipEventRecord(ev1, s));
-  int32_t h_err = 0;
-  HIP_TRY(hipMemcpyAsync(&h_err, err.p, sizeof(h_err), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_err) return h_err;
-  if (report) {
-    *report = acc;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  rg.r = nullptr;
-  *out = res;
-  return MI355Q_OK;
-}
-
-// Grouped steps over fact JOIN dim (SURVEY f2 + GROUP BY: `SELECT f.g, SUM(d.w), COUNT(*) FROM f JOIN d ON f.k = d.k GROUP BY
-// f.g`) with a ONE-TO-ONE join table over a large outer input.  In the row kernel every row probes the table AND updates its
-// group with device atomics; here the probe is its own pass (k_join_gather): per outer row, the inner columns the aggregates
-// read become dense temporary OUTER columns — the column's NULL where the row has no match — plus, for INNER joins, a 0 / 1
-// "matched" column the derived step filters on.  The derived plan has no join, the same targets over those columns and the
-// SAME layout (asserted: the descriptor of the derived plan must equal the stated one bit for bit), so its result is the
-// step's result and every grouped family applies (LDS members, the partitioned families).  One-to-many tables change the
-// row multiplicity and stay in the row kernel.  kNotTaken when the shape does not call for it.
-int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
-                            const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  if (plan->join_outer_col < 0 || plan->n_group_cols < 1 || plan->n_exprs != 0 || o.kernel_variant == 1 || o.force_generic ||
-      (d.join_hash_type != 0 && d.join_hash_type != 1) || q.desc_type == MI355Q_NON_GROUPED_AGGREGATE)
-    return kNotTaken;
-  const int nc = plan->n_cols, nf = in->n_frags;
-  const bool inner_join = plan->join_kind != MI355Q_JOIN_LEFT;
-  int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return kNotTaken;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
-  // (kernel_variant 2 = "the large-input members": how the tests reach this route with small tables)
-  if (nf < 1 || (o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
-  // a perfect-hash table of <= 64 KB is aggregated by the row kernel in a per-workgroup LDS copy (launch_generic): probe and
-  // update in one pass, nothing gained by splitting them — measured at 1 B rows, 100 groups: 49 ms there, 57 ms here; 10 000
-  // groups (global atomics there): 470 / 163 ms there (LEFT / INNER), 69 / 64 ms here (profiles/r04_grouped_join_1b_call16/17.jsonl)
-  if (o.kernel_variant != 2 && q.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && q.entry_count * (int64_t)q.row_size <= 64 * 1024)
-    return kNotTaken;
-  // the inner columns the targets read, in order of first use
-  int32_t used[MI355Q_MAX_COLS], dst[MI355Q_MAX_COLS], width[MI355Q_MAX_COLS];
-  int64_t null_pat[MI355Q_MAX_COLS];
-  int n_used = 0;
-  mi355q_plan p2 = *plan;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const mi355q_target& tg = plan->targets[t];
-    if (tg.agg == MI355Q_PROJECT_KEY || tg.table == 0 || tg.col < 0) continue;
-    if (tg.col >= plan->n_inner_cols) return kNotTaken;
-    int j = 0;
-    while (j < n_used && used[j] != tg.col) ++j;
-    if (j == n_used) {
-      const mi355q_col_desc& cd = plan->inner_cols[tg.col];
-      if (cd.encoding != MI355Q_ENC_NONE || (cd.logical_type != 0 && cd.logical_type != cd.type)) return kNotTaken;
-      if (nc + n_used + 1 + (inner_join ? 1 : 0) > MI355Q_MAX_COLS) return kNotTaken;
-      used[n_used] = tg.col;
-      dst[n_used] = nc + n_used;
-      width[n_used] = plain_width(cd.type);
-      null_pat[n_used] = cd.type == MI355Q_DOUBLE ? kNullDoubleBits
-                         : cd.type == MI355Q_FLOAT ? (int64_t)(uint32_t)kNullFloatBits : plain_int_null(cd.type);
-      p2.cols[nc + n_used] = cd;
-      // (nullable under an outer join, resolve_targets' rule; the RANGE stays the column's own, as the layout decisions read it)
-      if (!inner_join) p2.cols[nc + n_used].nullable = 1;
-      p2.col_ranges[nc + n_used] = plan->inner_col_ranges[tg.col];
-      ++n_used;
-    }
-    p2.targets[t].table = 0;
-    p2.targets[t].col = nc + j;
-  }
-  int flag_col = -1;
-  if (inner_join) {
-    if (plan->n_quals >= MI355Q_MAX_QUALS) return kNotTaken;
-    flag_col = nc + n_used;
-    p2.cols[flag_col] = mi355q_col_desc{MI355Q_INT32, 0, MI355Q_ENC_NONE, 0};  // (INT32: the fast families' range filters read INT32 / INT64)
-    p2.col_ranges[flag_col] = mi355q_range{1, 0, 0, 1, 0.0, 0.0, 0};
-    mi355q_qual& mq = p2.quals[p2.n_quals++];
-    mq = mi355q_qual{};
-    mq.col = flag_col;
-    mq.op = MI355Q_EQ;
-    mq.ival = 1;
-  }
-  const int nc2 = nc + n_used + (inner_join ? 1 : 0);
-  p2.n_cols = nc2;
-  p2.join_outer_col = -1;
-  p2.join_table = nullptr;
-  p2.n_join_cols = 0;
-  p2.join_kind = MI355Q_JOIN_INNER;
-  p2.n_inner_cols = 0;
-  mi355q_qmd q2;
-  if (qmd_init(p2, &q2) != MI355Q_OK || std::memcmp(&q, &q2, sizeof(q)) != 0) return kNotTaken;  // the same layout, or not this way
-  int64_t row_bytes = inner_join ? 4 : 0;
-  for (int j = 0; j < n_used; ++j) row_bytes += width[j];
-  mi355q_exec_options o2 = o;
-  if (reserved) {
-    route_note("k_join_gather (inner columns + matched flag as outer columns)");
-    // the derived step's shape: the same fragments with nc2 columns (the pointers are not looked at in reserve mode)
-    std::vector<const void*> fake((size_t)nf * nc2, nullptr);
-    mi355q_inputs in2 = *in;
-    in2.col_buffers = fake.data();
-    in2.inner_col_buffers = nullptr;
-    return execute_impl(&p2, &in2, &o2, out, report, nullptr, reserved);
-  }
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  const int64_t budget = std::min<int64_t>((int64_t)16 << 30, ((int64_t)free_b + ctx.gather_bytes) / 3);
-  const int64_t pad = 16 * (int64_t)(nc2 - nc);  // every (fragment, column) chunk starts on a 16-byte boundary
-  int64_t pass_rows = std::max<int64_t>(budget / std::max<int64_t>(row_bytes, 1), max_frag_rows);
-  if (o.pass_rows > 0) pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);  // tests: several passes
-  if (pass_rows > total_rows) pass_rows = total_rows;
-  const int64_t tab_bytes = ((int64_t)sizeof(void*) * nf * nc2 + 255) & ~255ll;
-  const int64_t rows_bytes = ((int64_t)sizeof(int64_t) * nf + 255) & ~255ll;
-  const int64_t col_region = ((pass_rows * row_bytes + pad * nf) + 255) & ~255ll;
-  const int64_t need = col_region + tab_bytes + rows_bytes + 256;
-  if (ctx.gather_bytes < need) {
-    if (ctx.gather) (void)hipFree(ctx.gather);
-    ctx.gather = nullptr;
-    ctx.gather_bytes = 0;
-    if (hipMalloc(&ctx.gather, (size_t)need) != hipSuccess) {
-      (void)hipGetLastError();
-      return kNotTaken;  // (the row kernel needs no temporary columns)
-    }
-    ctx.gather_bytes = need;
-  }
-  char* base = (char*)ctx.gather;
-  const int8_t** d_tab = (const int8_t**)(base + col_region);
-  int64_t* d_rows = (int64_t*)(base + col_region + tab_bytes);
-  HIP_TRY(hipMemcpyAsync(d_rows, in->num_rows, sizeof(int64_t) * (size_t)nf, hipMemcpyHostToDevice, s));
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-  std::vector<const void*> cols2((size_t)nf * nc2);
-  mi355q_result* res = nullptr;
-  struct ResGuard {
-    mi355q_result*& r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  mi355q_exec_report acc{};
-  int pass = 0, f = 0;
-  while (f < nf) {
-    int f1 = f;
-    int64_t rows = 0, off = 0;
-    while (f1 < nf && (f1 == f || rows + in->num_rows[f1] <= pass_rows)) {
-      for (int c = 0; c < nc; ++c) cols2[(size_t)(f1 - f) * nc2 + c] = in->col_buffers[(size_t)f1 * nc + c];
-      for (int k = nc; k < nc2; ++k) {
-        cols2[(size_t)(f1 - f) * nc2 + k] = base + off;
-        const int w = k == flag_col ? 4 : width[k - nc];
-        off += (in->num_rows[f1] * w + 15) & ~15ll;
-      }
-      rows += in->num_rows[f1];
-      ++f1;
-    }
-    if (off > col_region) return MI355Q_ERR_OUT_OF_GPU_MEM;  // (cannot happen: the region is sized for it)
-    const int pnf = f1 - f;
-    HIP_TRY(hipMemcpyAsync(d_tab, cols2.data(), sizeof(void*) * (size_t)pnf * nc2, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_join_gather(d, n_used, used, dst, width, null_pat, flag_col, nc2, d_tab, d_rows + f, pnf, max_frag_rows, n_cus, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (cols2 is re-used by the next pass; the step below synchronises anyway)
-    mi355q_inputs in2 = *in;
-    in2.n_frags = pnf;
-    in2.col_buffers = cols2.data();
-    in2.num_rows = in->num_rows + f;
-    in2.inner_col_buffers = nullptr;
-    o2 = o;
-    o2.stream = s;
-    o2.out_buffer = pass == 0 ? o.out_buffer : nullptr;
-    mi355q_result* r2 = nullptr;
-    mi355q_exec_report rep2{};
-    if (int32_t e2 = mi355q_execute(&p2, &in2, &o2, &r2, &rep2)) return e2;
-    if (pass == 0) {
-      res = r2;
-      std::snprintf(acc.kernel_name, sizeof(acc.kernel_name), "%s", rep2.kernel_name);
-      acc.variant = rep2.variant;
-    } else {
-      const int32_t er = mi355q_result_reduce(res, r2, s);
-      mi355q_result_free(r2);
-      if (er) return er;
-    }
-    acc.kernel_ms += rep2.kernel_ms;
-    acc.n_launches += rep2.n_launches + 1;
-    acc.spilled_rows += rep2.spilled_rows;
-    f = f1;
-    ++pass;
-  }
-  if (ev1) HIP_TRY(hipEventRecord(ev1, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (report) {
-    *report = acc;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  *out = res;
-  res = nullptr;
-  return MI355Q_OK;
-}
-
-// Baseline steps over 2 - 3 plain INT key columns that all have ranges — the reference's PerfectHashMultiCol / MultiStep
-// shapes beyond g_baseline_groupby_threshold (PHM006, MSPHM005, MSPHM007: ~11 M combinations, Execute.cpp:113,
-// GroupByAndAggregate.cpp:232-365) — over a large input: the product of the ranges still indexes a table the
-// index-partitioned family (kernels_idx.hip) aggregates in one exchange, so the step runs on a library-owned PERFECT
-// twin of the layout and its live entries are re-keyed into the baseline table of the stated plan
-// (kernels_generic.hip k_perfect_twin_emit).  kNotTaken when the shape does not call for it.
-constexpr int64_t kTwinMaxEntries = (int64_t)32 << 20;
-int32_t execute_perfect_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
-                             int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  if (q.desc_type != MI355Q_GROUP_BY_BASELINE_HASH || plan->n_group_cols < 2 || plan->n_group_cols > 3 ||
-      plan->join_outer_col >= 0 || plan->n_exprs != 0 || q.slot_width != 8 || q.output_columnar ||
-      plan->output_columnar_hint != 0 || o.kernel_variant == 1 || o.force_generic)
-    return kNotTaken;
-  __int128 card = 1;
-  int32_t translate[MI355Q_MAX_GROUP_COLS], key_type[MI355Q_MAX_GROUP_COLS];
-  for (int g = 0; g < plan->n_group_cols; ++g) {
-    const int c = plan->group_cols[g];
-    if (c < 0 || c >= plan->n_cols) return kNotTaken;
-    const mi355q_col_desc& cd = plan->cols[c];
-    const mi355q_range& r = plan->col_ranges[c];
-    if (cd.type != MI355Q_INT32 || cd.encoding != MI355Q_ENC_NONE || (cd.logical_type != 0 && cd.logical_type != cd.type) ||
-        !r.valid || r.bucket != 0 || r.min > r.max || (r.has_nulls && !cd.nullable))
-      return kNotTaken;
-    card *= (__int128)r.max - (__int128)r.min + 1 + (r.has_nulls ? 1 : 0);
-    if (card > (__int128)kTwinMaxEntries) return kNotTaken;
-    translate[g] = cd.nullable && r.has_nulls;  // (build_dev_plan's rule for several key columns)
-    key_type[g] = col_type_code(cd);
-  }
-  int64_t total_rows = 0, max_rows = 0;
-  for (int f = 0; f < in->n_frags; ++f) {
-    total_rows += in->num_rows[f];
-    max_rows = std::max(max_rows, in->num_rows[f]);
-  }
-  // (kernel_variant 2 = "the large-input members": how the tests reach this route with small tables)
-  if (o.kernel_variant != 2 && total_rows < kIdxPartMinRows) return kNotTaken;
-  PerfectTwinScope twin(kTwinMaxEntries);
-  mi355q_qmd q2;
-  if (qmd_init(*plan, &q2) != MI355Q_OK) return kNotTaken;
-  if (q2.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || q2.slot_width != 8 || q2.output_columnar ||
-      q2.entry_count * (int64_t)q2.row_size > ((int64_t)4 << 30))
-    return kNotTaken;
-  DevPlan d2;
-  if (build_dev_plan(*plan, q2, &d2) != MI355Q_OK) return kNotTaken;
-  {
-    FragView fvh{nullptr, nullptr, in->col_buffers, in->num_rows, in->n_frags, plan->n_cols, total_rows, max_rows};
-    if (!idx_part_eligible(d2, fvh, n_cus)) return kNotTaken;
-  }
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const int sf = q.target_slot[t], ss = q2.target_slot[t];
-    if (plan->targets[t].agg == MI355Q_PROJECT_KEY) {
-      if (sf >= 0) return kNotTaken;  // (baseline: projections are read from the key columns)
-      continue;
-    }
-    if (sf < 0 || ss < 0) return kNotTaken;
-    for (int j = 0; j < (plan->targets[t].agg == MI355Q_AVG ? 2 : 1); ++j)
-      if (q.init_vals[sf + j] != q2.init_vals[ss + j]) return kNotTaken;
-  }
-  mi355q_exec_options o2 = o;
-  o2.out_buffer = nullptr;
-  if (reserved) {
-    route_note("perfect-hash twin + k_perfect_twin_emit");
-    return execute_impl(plan, in, &o2, out, report, nullptr, reserved);
-  }
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-  o2.stream = s;
-  mi355q_result* r2 = nullptr;
-  mi355q_exec_report rep2{};
-  if (int32_t e2 = mi355q_execute(plan, in, &o2, &r2, &rep2)) {
-    if (e2 == MI355Q_ERR_UNSUPPORTED || e2 == MI355Q_ERR_OUT_OF_GPU_MEM || e2 < 0) return kNotTaken;
-    return e2;
-  }
-  struct R2Guard {
-    mi355q_result* r;
-    ~R2Guard() { if (r) mi355q_result_free(r); }
-  } r2g{r2};
-  if (r2->qmd.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || r2->qmd.slot_width != 8 || r2->qmd.output_columnar ||
-      r2->qmd.entry_count != q2.entry_count)
-    return kNotTaken;
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  DevWord err;
-  HIP_TRY(hipMalloc(&err.p, 64));
-  HIP_TRY(hipMemsetAsync(err.p, 0, 64, s));
-  HIP_TRY(launch_perfect_twin_emit(res->dplan, r2->dplan, r2->qmd.idx_target_as_key, plan->n_group_cols, translate, key_type,
-                                   q2.group_min, q2.group_card, q2.group_null_key, r2->buf, res->buf, (int32_t*)err.p, s));
-  if (ev1) HIP_TRY(hipEventRecord(ev1, s));
-  int32_t h_err = 0;
-  HIP_TRY(hipMemcpyAsync(&h_err, err.p, sizeof(h_err), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_err) return h_err;
-  if (report) {
-    *report = rep2;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->n_launches = rep2.n_launches + 1;
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  rg.r = nullptr;
-  *out = res;
-  return MI355Q_OK;
-}
-
-// Baseline steps whose key columns lie on a LATTICE — key = min + stride x i — with few lattice points: the reference
-// benchmark's BIGINT columns x10k_s10k / x100k_s10k / x1m_s10k (multiples of 10 000: BaselineHash/BH007-010,
-// MultiStep/MSBS006-007).  Their RANGE is far too wide for a perfect hash (GroupByAndAggregate.cpp:232-365 sees max - min),
-// so the reference — and the plain route here — hash 8-byte keys.  The stride is found on the first fragment (k_key_gcd), every
-// row's key is then rewritten as its lattice index i in a dense INT32 column and CHECKED (k_affine_keys: a key off the
-// lattice or outside the range gives the route up, nothing is assumed about the data), the step runs grouped by those
-// columns on a library-owned perfect-hash twin (typed LDS members / the index-partitioned family: ONE exchange of 8- or
-// 16-byte records instead of 16-byte records per value column), and k_affine_twin_emit re-keys the twin's entries into the
-// baseline table of the stated plan.  mi355q_explain cannot see the data and names the plain route for these shapes.
-int32_t execute_affine_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
-                            int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  if (reserved || q.desc_type != MI355Q_GROUP_BY_BASELINE_HASH || plan->n_group_cols < 1 || plan->n_group_cols > 3 ||
-      plan->join_outer_col >= 0 || plan->n_exprs != 0 || q.slot_width != 8 || q.output_columnar ||
-      plan->output_columnar_hint != 0 || o.kernel_variant == 1 || o.force_generic)
-    return kNotTaken;
-  const int nc = plan->n_cols, nf = in->n_frags, ng = plan->n_group_cols;
-  int64_t total_rows = 0, max_frag_rows = 0;
-  int first = -1;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return kNotTaken;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-    if (first < 0 && in->num_rows[f] > 0) first = f;
-  }
-  // (kernel_variant 2 = "the large-input members": how the tests reach this route with small tables)
-  if (first < 0 || (o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
-  bool proj[MI355Q_MAX_GROUP_COLS];
-  int n_proj = 0;
-  for (int g = 0; g < ng; ++g) {
-    const int c = plan->group_cols[g];
-    if (c < 0 || c >= nc) return kNotTaken;
-    const mi355q_col_desc& cd = plan->cols[c];
-    const mi355q_range& r = plan->col_ranges[c];
-    if ((cd.type != MI355Q_INT32 && cd.type != MI355Q_INT64) || cd.encoding != MI355Q_ENC_NONE ||
-        (cd.logical_type != 0 && cd.logical_type != cd.type) || !r.valid || r.bucket != 0 || r.min > r.max ||
-        (r.has_nulls && !cd.nullable))
-      return kNotTaken;
-    // BIGINT keys, and INT keys over a range too wide for the twin on their own, are looked at for a stride
-    proj[g] = cd.type == MI355Q_INT64 || (__int128)r.max - (__int128)r.min >= ((__int128)1 << 20);
-    n_proj += proj[g] ? 1 : 0;
-  }
-  if (n_proj == 0 || nc + n_proj > MI355Q_MAX_COLS) return kNotTaken;
-  // only where the twin's step is the typed LDS members' or the index-partitioned family's work (no qual, plain INT value
-  // columns: checked here before anything is launched, and on the derived plan below): every other baseline step — the
-  // headline's filtered AVG(double) among them — keeps its own family and pays nothing for this route
-  // (a compiled filter travelling beside the plan is a qual too: the `rest` plan of execute_bool_filter has n_quals = 0;
-  // ADVICE r05)
-  if (plan->n_quals != 0 || step_bool_filter()) return kNotTaken;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const mi355q_target& tg = plan->targets[t];
-    if (tg.agg == MI355Q_PROJECT_KEY || tg.col < 0) continue;
-    if (tg.table != 0 || tg.col >= nc || tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF) return kNotTaken;
-    const mi355q_col_desc& vd = plan->cols[tg.col];
-    if (vd.type != MI355Q_INT32 || vd.encoding != MI355Q_ENC_NONE || (vd.logical_type != 0 && vd.logical_type != vd.type)) return kNotTaken;
-  }
-
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  // ---- the stride of every looked-at key column, from the first non-empty fragment
-  // (a sample: the first 4 M rows — the stride it gives is verified on every row below, a coarser lattice only gives the route up)
-  constexpr int kGcdBlocks = 256;  // partial strides per column handed to the host
-  constexpr int64_t kGcdScratch = 64 * 256;
-  DevWord gw;
-  HIP_TRY(hipMalloc(&gw.p, sizeof(unsigned long long) * (kGcdScratch + kGcdBlocks * MI355Q_MAX_GROUP_COLS) + 64));
-  unsigned long long* g_scr = (unsigned long long*)gw.p;
-  unsigned long long* g_out = g_scr + kGcdScratch;
-  std::vector<unsigned long long> h_g((size_t)kGcdBlocks * MI355Q_MAX_GROUP_COLS);
-  for (int gcol = 0, k = 0; gcol < ng; ++gcol) {
-    if (!proj[gcol]) continue;
-    const int c = plan->group_cols[gcol];
-    HIP_TRY(launch_key_gcd(in->col_buffers[(size_t)first * nc + c], plain_width(plan->cols[c].type),
-                           std::min<int64_t>(in->num_rows[first], (int64_t)4 << 20), plan->col_ranges[c].min, plan->cols[c].nullable, g_scr,
-                           g_out + (size_t)k * kGcdBlocks, s));
-    ++k;
-  }
-  HIP_TRY(hipMemcpyAsync(h_g.data(), g_out, sizeof(unsigned long long) * kGcdBlocks * n_proj, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  // ---- the derived plan
-  mi355q_plan p2 = *plan;
-  int32_t src_col[MI355Q_MAX_GROUP_COLS], dst_col[MI355Q_MAX_GROUP_COLS], width[MI355Q_MAX_GROUP_COLS], nullable[MI355Q_MAX_GROUP_COLS];
-  int64_t kmin[MI355Q_MAX_GROUP_COLS], stride[MI355Q_MAX_GROUP_COLS], card[MI355Q_MAX_GROUP_COLS];
-  int64_t base_of[MI355Q_MAX_GROUP_COLS], stride_of[MI355Q_MAX_GROUP_COLS];
-  int32_t translate[MI355Q_MAX_GROUP_COLS], key_type[MI355Q_MAX_GROUP_COLS];
-  __int128 entries = 1;
-  for (int gcol = 0, k = 0; gcol < ng; ++gcol) {
-    const int c = plan->group_cols[gcol];
-    const mi355q_col_desc& cd = plan->cols[c];
-    const mi355q_range& r = plan->col_ranges[c];
-    translate[gcol] = cd.nullable && (ng == 1 || r.has_nulls);  // (build_dev_plan's rule for the twin's keys)
-    key_type[gcol] = col_type_code(cd);
-    base_of[gcol] = r.min;
-    stride_of[gcol] = 1;
-    __int128 points = (__int128)r.max - (__int128)r.min + 1;
-    if (proj[gcol]) {
-      unsigned long long gg = 0;
-      for (int b = 0; b < kGcdBlocks; ++b) {
-        unsigned long long x = h_g[(size_t)k * kGcdBlocks + b], y = gg;
-        while (y) {
-          const unsigned long long t = x % y;
-          x = y;
-          y = t;
-        }
-        gg = x;
-      }
-      if (gg == 0) gg = 1;  // (every key of the fragment is the minimum, or NULL)
-      if (gg > (unsigned long long)INT64_MAX) return kNotTaken;
-      points = ((__int128)r.max - (__int128)r.min) / (__int128)gg + 1;
-      if (points >= ((__int128)1 << 30)) return kNotTaken;
-      stride_of[gcol] = (int64_t)gg;
-      src_col[k] = c;
-      dst_col[k] = nc + k;
-      width[k] = plain_width(cd.type);
-      nullable[k] = cd.nullable;
-      kmin[k] = r.min;
-      stride[k] = (int64_t)gg;
-      card[k] = (int64_t)points;
-      p2.cols[nc + k] = mi355q_col_desc{MI355Q_INT32, cd.nullable, MI355Q_ENC_NONE, 0};
-      p2.col_ranges[nc + k] = mi355q_range{1, r.has_nulls, 0, (int64_t)points - 1, 0.0, 0.0, 0};
-      p2.group_cols[gcol] = nc + k;
-      ++k;
-    } else if (points >= ((__int128)1 << 30) || r.min <= -((int64_t)1 << 30) || r.min >= ((int64_t)1 << 30)) {
-      return kNotTaken;
-    }
-    entries *= points + (r.has_nulls ? 1 : 0);
-    if (entries > (__int128)kTwinMaxEntries) return kNotTaken;
-  }
-  // one key, one value column, >= 512 K lattice points: the 16-byte partitioned family does this shape as well as the twin's
-  // two extra passes allow (BH009 at 1 B rows: 8.6 ms there, 9.9 ms here; 100 K points, BH008: 12.5 -> 8.2 ms;
-  // profiles/r04_refbench_lattice_keys_call21.jsonl)
-  {
-    int vcols[MI355Q_MAX_TARGETS], n_v = 0;
-    for (int t = 0; t < plan->n_targets; ++t) {
-      const mi355q_target& tg = plan->targets[t];
-      if (tg.agg == MI355Q_PROJECT_KEY || tg.col < 0) continue;
-      bool seen = false;
-      for (int k = 0; k < n_v; ++k) seen = seen || vcols[k] == tg.col;
-      if (!seen) vcols[n_v++] = tg.col;
-    }
-    if (ng == 1 && n_v <= 1 && entries >= ((__int128)1 << 19) && o.kernel_variant != 2) return kNotTaken;
-  }
-  const int nc2 = nc + n_proj;
-  p2.n_cols = nc2;
-  PerfectTwinScope twin(kTwinMaxEntries);
-  mi355q_qmd q2;
-  if (qmd_init(p2, &q2) != MI355Q_OK) return kNotTaken;
-  if (q2.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || q2.slot_width != 8 || q2.output_columnar ||
-      q2.entry_count * (int64_t)q2.row_size > ((int64_t)4 << 30))
-    return kNotTaken;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const int sf = q.target_slot[t], ss = q2.target_slot[t];
-    if (plan->targets[t].agg == MI355Q_PROJECT_KEY) {
-      if (sf >= 0) return kNotTaken;  // (baseline: projections are read from the key columns)
-      continue;
-    }
-    if (sf < 0 || ss < 0) return kNotTaken;
-    for (int j = 0; j < (plan->targets[t].agg == MI355Q_AVG ? 2 : 1); ++j)
-      if (q.init_vals[sf + j] != q2.init_vals[ss + j]) return kNotTaken;
-  }
-  {  // the twin's step must be one of the two families this route is for
-    DevPlan d2;
-    if (build_dev_plan(p2, q2, &d2) != MI355Q_OK) return kNotTaken;
-    std::vector<const void*> shape((size_t)nf * nc2);
-    for (int f = 0; f < nf; ++f) {
-      for (int c = 0; c < nc; ++c) shape[(size_t)f * nc2 + c] = in->col_buffers[(size_t)f * nc + c];
-      for (int k = 0; k < n_proj; ++k) shape[(size_t)f * nc2 + nc + k] = (const void*)(uintptr_t)256;  // (16-byte aligned, like the real chunks)
-    }
-    FragView fvh{nullptr, nullptr, shape.data(), in->num_rows, nf, nc2, total_rows, max_frag_rows};
-    if (!lds_groupby_eligible(d2, fvh, n_cus) && !idx_part_eligible(d2, fvh, n_cus)) return kNotTaken;
-  }
-  // ---- passes: lattice indices of a pass of fragments, the twin step on them
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  const int64_t budget = std::min<int64_t>((int64_t)16 << 30, ((int64_t)free_b + ctx.lattice_bytes) / 3);
-  const int64_t row_bytes = 4 * (int64_t)n_proj, pad = 16 * (int64_t)n_proj;
-  int64_t pass_rows = std::max<int64_t>(budget / row_bytes, max_frag_rows);
-  if (o.pass_rows > 0) pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);  // tests: several passes
-  if (pass_rows > total_rows) pass_rows = total_rows;
-  const int64_t tab_bytes = ((int64_t)sizeof(void*) * nf * nc2 + 255) & ~255ll;
-  const int64_t rows_bytes = ((int64_t)sizeof(int64_t) * nf + 255) & ~255ll;
-  const int64_t col_region = ((pass_rows * row_bytes + pad * nf) + 255) & ~255ll;
-  const int64_t need = col_region + tab_bytes + rows_bytes + 256;
-  if (ctx.lattice_bytes < need) {
-    if (ctx.lattice) (void)hipFree(ctx.lattice);
-    ctx.lattice = nullptr;
-    ctx.lattice_bytes = 0;
-    if (hipMalloc(&ctx.lattice, (size_t)need) != hipSuccess) {
-      (void)hipGetLastError();
-      return kNotTaken;
-    }
-    ctx.lattice_bytes = need;
-  }
-  char* base = (char*)ctx.lattice;
-  const int8_t** d_tab = (const int8_t**)(base + col_region);
-  int64_t* d_rows = (int64_t*)(base + col_region + tab_bytes);
-  int32_t* d_flag = (int32_t*)(base + col_region + tab_bytes + rows_bytes);
-  HIP_TRY(hipMemsetAsync(d_flag, 0, 64, s));
-  HIP_TRY(hipMemcpyAsync(d_rows, in->num_rows, sizeof(int64_t) * (size_t)nf, hipMemcpyHostToDevice, s));
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-  std::vector<const void*> cols2((size_t)nf * nc2);
-  mi355q_result* tw = nullptr;  // the twin table (all passes folded)
-  struct TwGuard {
-    mi355q_result*& r;
-    ~TwGuard() { if (r) mi355q_result_free(r); }
-  } twg{tw};
-  mi355q_exec_report acc{};
-  int pass = 0, f = 0;
-  while (f < nf) {
-    int f1 = f;
-    int64_t rows = 0, off = 0;
-    while (f1 < nf && (f1 == f || rows + in->num_rows[f1] <= pass_rows)) {
-      for (int c = 0; c < nc; ++c) cols2[(size_t)(f1 - f) * nc2 + c] = in->col_buffers[(size_t)f1 * nc + c];
-      for (int k = 0; k < n_proj; ++k) {
-        cols2[(size_t)(f1 - f) * nc2 + nc + k] = base + off;
-        off += (in->num_rows[f1] * 4 + 15) & ~15ll;
-      }
-      rows += in->num_rows[f1];
-      ++f1;
-    }
-    if (off > col_region) return MI355Q_ERR_OUT_OF_GPU_MEM;  // (cannot happen: the region is sized for it)
-    const int pnf = f1 - f;
-    HIP_TRY(hipMemcpyAsync(d_tab, cols2.data(), sizeof(void*) * (size_t)pnf * nc2, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_affine_keys(n_proj, src_col, dst_col, width, nullable, kmin, stride, card, nc2, d_tab, d_rows + f, pnf, max_frag_rows,
-                               d_flag, n_cus, s));
-    int32_t h_flag = 0;
-    HIP_TRY(hipMemcpyAsync(&h_flag, d_flag, sizeof(h_flag), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h_flag) return kNotTaken;  // a key off the lattice of the first fragment: the plain route
-    mi355q_inputs in2 = *in;
-    in2.n_frags = pnf;
-    in2.col_buffers = cols2.data();
-    in2.num_rows = in->num_rows + f;
-    mi355q_exec_options o2 = o;
-    o2.stream = s;
-    o2.out_buffer = nullptr;
-    mi355q_result* r2 = nullptr;
-    mi355q_exec_report rep2{};
-    if (int32_t e2 = mi355q_execute(&p2, &in2, &o2, &r2, &rep2)) {
-      if (e2 == MI355Q_ERR_UNSUPPORTED || e2 == MI355Q_ERR_OUT_OF_GPU_MEM || e2 < 0 || e2 == MI355Q_ERR_OUT_OF_SLOTS) return kNotTaken;
-      return e2;
-    }
-    if (r2->qmd.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || r2->qmd.slot_width != 8 || r2->qmd.output_columnar ||
-        r2->qmd.entry_count != q2.entry_count) {
-      mi355q_result_free(r2);
-      return kNotTaken;
-    }
-    if (pass == 0) {
-      tw = r2;
-      std::snprintf(acc.kernel_name, sizeof(acc.kernel_name), "%s", rep2.kernel_name);
-      acc.variant = rep2.variant;
-    } else {
-      const int32_t er = mi355q_result_reduce(tw, r2, s);
-      mi355q_result_free(r2);
-      if (er) return er;
-    }
-    acc.kernel_ms += rep2.kernel_ms;
-    acc.n_launches += rep2.n_launches + 1;
-    acc.spilled_rows += rep2.spilled_rows;
-    f = f1;
-    ++pass;
-  }
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  DevWord err;
-  HIP_TRY(hipMalloc(&err.p, 64));
-  HIP_TRY(hipMemsetAsync(err.p, 0, 64, s));
-  HIP_TRY(launch_affine_twin_emit(res->dplan, tw->dplan, tw->qmd.idx_target_as_key, ng, translate, key_type, q2.group_min, q2.group_card,
-                                  q2.group_null_key, base_of, stride_of, tw->buf, res->buf, (int32_t*)err.p, s));
-  if (ev1) HIP_TRY(hipEventRecord(ev1, s));
-  int32_t h_err = 0;
-  HIP_TRY(hipMemcpyAsync(&h_err, err.p, sizeof(h_err), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_err) return h_err;
-  if (report) {
-    *report = acc;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->n_launches = acc.n_launches + 1;
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  rg.r = nullptr;
-  *out = res;
-  return MI355Q_OK;
-}
-
-// GROUP BY CAST(<plain integer column> AS DOUBLE | FLOAT) — the reference benchmark's BaselineHash and MultiStep
-// BaselineHash shapes (Benchmarks/synthetic_benchmark/queries/BaselineHash/BH001-006.sql, MultiStep/MSBS001-005.sql).  A
-// floating-point key always takes the baseline layout (GroupByAndAggregate.cpp:232-365: getExprRangeInfo is FloatingPoint),
-// but the groups ARE the integer column's values: the step runs on a derived plan that groups by the integer column
-// itself (perfect hash: the LDS / partitioned families, no key expression to project), and its entries are then re-keyed
-// with the cast value and merged into the baseline table of the stated plan (kernels_generic.hip k_cast_key_emit).
-// kNotTaken when the shape does not call for it.
-// Does an expression of the plan read the value of another one (MI355Q_EX_COL with arg >= n_cols)?  The derived-plan routes
-// below take expressions out of the plan and renumber the rest: they leave such plans to the projection.
-bool exprs_read_exprs(const mi355q_plan& p) {
-  for (int k = 0; k < p.n_exprs && k < MI355Q_MAX_EXPRS; ++k)
-    for (int i = 0; i < p.exprs[k].n_nodes && i < MI355Q_MAX_EXPR_NODES; ++i)
-      if (p.exprs[k].nodes[i].op == MI355Q_EX_COL && p.exprs[k].nodes[i].arg >= p.n_cols) return true;
-  return false;
-}
-
-int32_t execute_cast_key(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
-                         mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  if (plan->n_group_cols != 1 || plan->join_outer_col >= 0 || plan->output_columnar_hint != 0 || o.kernel_variant == 1 ||
-      o.force_generic || exprs_read_exprs(*plan))
-    return kNotTaken;
-  const int nc = plan->n_cols, gc = plan->group_cols[0];
-  if (gc < nc || gc >= nc + plan->n_exprs) return kNotTaken;
-  const mi355q_expr& ex = plan->exprs[gc - nc];
-  if (ex.n_nodes != 2 || ex.nodes[0].op != MI355Q_EX_COL || ex.nodes[1].op != MI355Q_EX_CAST) return kNotTaken;
-  const int to = ex.nodes[1].type, c = ex.nodes[0].arg;
-  if ((to != MI355Q_DOUBLE && to != MI355Q_FLOAT) || c < 0 || c >= nc) return kNotTaken;
-  const mi355q_col_desc& cd = plan->cols[c];
-  const mi355q_range& cr = plan->col_ranges[c];
-  if ((cd.type != MI355Q_INT32 && cd.type != MI355Q_INT64) || cd.encoding != MI355Q_ENC_NONE ||
-      (cd.logical_type != 0 && cd.logical_type != cd.type) || !cr.valid || cr.bucket != 0 || (cr.has_nulls && !cd.nullable))
-    return kNotTaken;
-  int64_t total_rows = 0;
-  for (int f = 0; f < in->n_frags; ++f) total_rows += in->num_rows[f];
-  // (kernel_variant 2 = "the large-input members": how the tests reach this route with small tables)
-  if (o.kernel_variant != 2 && total_rows < ((int64_t)4 << 20)) return kNotTaken;
-  // the derived plan: the key expression leaves, the expressions behind it move down one column
-  mi355q_plan p2 = *plan;
-  p2.group_cols[0] = c;
-  for (int e = gc - nc; e + 1 < plan->n_exprs; ++e) p2.exprs[e] = plan->exprs[e + 1];
-  p2.n_exprs = plan->n_exprs - 1;
-  bool key_read = false;
-  auto move = [&](int32_t& col) {
-    key_read = key_read || col == gc;
-    if (col > gc) --col;
-  };
-  for (int t = 0; t < p2.n_targets; ++t) {
-    mi355q_target& tg = p2.targets[t];
-    if (tg.agg == MI355Q_PROJECT_KEY) continue;
-    if (tg.table == 0 && tg.col >= 0) move(tg.col);
-    if (tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF) move(tg.cond.col);
-  }
-  for (int i = 0; i < p2.n_quals; ++i) move(p2.quals[i].col);
-  if (key_read) return kNotTaken;  // the cast value itself is aggregated or filtered on
-  mi355q_qmd q, q2;
-  if (qmd_init(*plan, &q) != MI355Q_OK || qmd_init(p2, &q2) != MI355Q_OK) return kNotTaken;
-  if (q.desc_type != MI355Q_GROUP_BY_BASELINE_HASH || q.slot_width != 8 || q.key_width != 8 || q.output_columnar ||
-      q2.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || q2.slot_width != 8 || q2.output_columnar)
-    return kNotTaken;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const int sf = q.target_slot[t], ss = q2.target_slot[t];
-    if (plan->targets[t].agg == MI355Q_PROJECT_KEY) {
-      if (sf >= 0) return kNotTaken;  // (baseline: projections are read from the key column)
-      continue;
-    }
-    if (sf < 0 || ss < 0) return kNotTaken;
-    for (int j = 0; j < (plan->targets[t].agg == MI355Q_AVG ? 2 : 1); ++j)
-      if (q.init_vals[sf + j] != q2.init_vals[ss + j]) return kNotTaken;
-  }
-  mi355q_exec_options o2 = o;
-  o2.out_buffer = nullptr;
-  if (reserved) {
-    route_note("the step grouped by the integer column + k_cast_key_emit");
-    return execute_impl(&p2, in, &o2, out, report, nullptr, reserved);
-  }
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-  o2.stream = s;
-  mi355q_result* r2 = nullptr;
-  mi355q_exec_report rep2{};
-  if (int32_t e2 = mi355q_execute(&p2, in, &o2, &r2, &rep2)) {
-    if (e2 == MI355Q_ERR_UNSUPPORTED || e2 == MI355Q_ERR_OUT_OF_GPU_MEM || e2 < 0) return kNotTaken;
-    return e2;
-  }
-  struct R2Guard {
-    mi355q_result* r;
-    ~R2Guard() { if (r) mi355q_result_free(r); }
-  } r2g{r2};
-  if (r2->qmd.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || r2->qmd.slot_width != 8 || r2->qmd.output_columnar ||
-      r2->qmd.entry_count != q2.entry_count || r2->qmd.group_min[0] != q2.group_min[0])
-    return kNotTaken;
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  DevWord err;
-  HIP_TRY(hipMalloc(&err.p, 64));
-  HIP_TRY(hipMemsetAsync(err.p, 0, 64, s));
-  // (NULL keys of a nullable column sit at max + 1: groupByColumnCodegen translate_null_val, as plan.cpp build_dev_plan)
-  HIP_TRY(launch_cast_key_emit(res->dplan, r2->dplan, r2->qmd.idx_target_as_key, to == MI355Q_FLOAT ? 1 : 0, cd.nullable != 0,
-                               q2.group_min[0], q2.group_null_key[0], r2->buf, res->buf, (int32_t*)err.p, s));
-  if (ev1) HIP_TRY(hipEventRecord(ev1, s));
-  int32_t h_err = 0;
-  HIP_TRY(hipMemcpyAsync(&h_err, err.p, sizeof(h_err), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_err) return h_err;
-  if (report) {
-    *report = rep2;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->n_launches = rep2.n_launches + 1;
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  rg.r = nullptr;
-  *out = res;
-  return MI355Q_OK;
-}
-
-// Aggregates whose argument is `plain INT column + / - literal` (the reference benchmark's MultiStep shapes:
-// MAX(x10 + 1), SUM(x10 + 1) next to MAX(x10)).  The reference compiles the addition into the row function
-// (ArithmeticIR.cpp:77-150); materialising it as a projected column costs a pass over the input and a value column of
-// the exchange.  Where the column's range says the addition cannot overflow, the step runs on a derived plan that
-// aggregates the COLUMN — MIN / MAX / SUM / AVG / COUNT of (x + L) are MIN(x) + L, MAX(x) + L, SUM(x) + L·COUNT(x),
-// (SUM(x) + L·COUNT(x)) / COUNT(x), COUNT(x), with NULL rows skipped on both sides and wrapping 64-bit sums — and the
-// literal is added while the derived table is copied into the stated layout (k_zip_targets).  The derived plan holds
-// every distinct aggregate once, plus COUNT(x) where a sum needs it.  kNotTaken when the shape does not call for it.
-int32_t execute_shifted_args(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
-                             mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  if (plan->n_group_cols < 1 || plan->join_outer_col >= 0 || plan->output_columnar_hint != 0 || o.kernel_variant == 1 ||
-      o.force_generic || exprs_read_exprs(*plan))
-    return kNotTaken;
-  const int nc = plan->n_cols, nx = plan->n_exprs;
-  // which expressions are `column +- literal` that cannot overflow
-  int src_col[MI355Q_MAX_EXPRS];
-  int64_t shift[MI355Q_MAX_EXPRS];
-  bool any = false;
-  for (int k = 0; k < nx; ++k) {
-    src_col[k] = -1;
-    const mi355q_expr& ex = plan->exprs[k];
-    if (ex.n_nodes != 3 || ex.nodes[0].op != MI355Q_EX_COL || ex.nodes[1].op != MI355Q_EX_LIT || ex.nodes[1].reserved != 0 ||
-        (ex.nodes[2].op != MI355Q_EX_ADD && ex.nodes[2].op != MI355Q_EX_SUB))
-      continue;
-    const int c = ex.nodes[0].arg;
-    if (c < 0 || c >= nc) continue;
-    const mi355q_col_desc& cd = plan->cols[c];
-    const mi355q_range& r = plan->col_ranges[c];
-    if ((cd.type != MI355Q_INT32 && cd.type != MI355Q_INT64) || cd.encoding != MI355Q_ENC_NONE ||
-        (cd.logical_type != 0 && cd.logical_type != cd.type) || ex.nodes[1].type != cd.type || ex.nodes[2].type != cd.type ||
-        !r.valid || r.min > r.max)
-      continue;
-    const __int128 L = ex.nodes[2].op == MI355Q_EX_ADD ? (__int128)ex.nodes[1].ilit : -(__int128)ex.nodes[1].ilit;
-    const __int128 tmax = cd.type == MI355Q_INT32 ? (__int128)INT32_MAX : (__int128)INT64_MAX;
-    // (the type's minimum is its NULL; the literal itself must be a value of the type)
-    if ((__int128)r.max + L > tmax || (__int128)r.min + L <= -tmax - 1 || L > tmax || L < -tmax) continue;
-    src_col[k] = c;
-    shift[k] = (int64_t)L;
-    any = true;
-  }
-  if (!any) return kNotTaken;
-  // an expression that is also a key, a filter column or a condition stays projected
-  for (int g = 0; g < plan->n_group_cols; ++g)
-    if (plan->group_cols[g] >= nc && plan->group_cols[g] < nc + nx) src_col[plan->group_cols[g] - nc] = -1;
-  for (int i = 0; i < plan->n_quals; ++i)
-    if (plan->quals[i].col >= nc && plan->quals[i].col < nc + nx) src_col[plan->quals[i].col - nc] = -1;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const mi355q_target& tg = plan->targets[t];
-    if ((tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF) && tg.cond.col >= nc && tg.cond.col < nc + nx)
-      src_col[tg.cond.col - nc] = -1;
-    if (tg.agg != MI355Q_PROJECT_KEY && tg.table == 0 && tg.col >= nc && tg.col < nc + nx &&
-        (tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF))
-      src_col[tg.col - nc] = -1;
-  }
-  any = false;
-  for (int k = 0; k < nx; ++k) any = any || src_col[k] >= 0;
-  if (!any) return kNotTaken;
-  int64_t total_rows = 0;
-  for (int f = 0; f < in->n_frags; ++f) total_rows += in->num_rows[f];
-  // (kernel_variant 2 = "the large-input members": how the tests reach this route with small tables)
-  if (o.kernel_variant != 2 && total_rows < ((int64_t)4 << 20)) return kNotTaken;
-
-  // the derived plan: the shifted expressions leave (the others move down), every distinct aggregate once
-  mi355q_plan p2 = *plan;
-  int new_col[MI355Q_MAX_EXPRS];  // column index of a kept expression in the derived plan
-  p2.n_exprs = 0;
-  for (int k = 0; k < nx; ++k) {
-    if (src_col[k] >= 0) {
-      new_col[k] = -1;
-    } else {
-      new_col[k] = nc + p2.n_exprs;
-      p2.exprs[p2.n_exprs++] = plan->exprs[k];
-    }
-  }
-  auto moved = [&](int col) { return col >= nc && col < nc + nx ? new_col[col - nc] : col; };
-  for (int g = 0; g < p2.n_group_cols; ++g) p2.group_cols[g] = moved(plan->group_cols[g]);
-  for (int i = 0; i < p2.n_quals; ++i) p2.quals[i].col = moved(plan->quals[i].col);
-  p2.n_targets = 0;
-  int t2_of[MI355Q_MAX_TARGETS], cnt_t2[MI355Q_MAX_TARGETS];  // final target -> derived target; -> the derived COUNT(x)
-  int64_t lit_of[MI355Q_MAX_TARGETS];
-  auto same = [](const mi355q_target& a, const mi355q_target& b) {
-    return a.agg == b.agg && a.col == b.col && a.table == b.table && a.cond.col == b.cond.col && a.cond.op == b.cond.op &&
-           a.cond.ival == b.cond.ival && a.cond.fval == b.cond.fval;
-  };
-  auto add_target = [&](const mi355q_target& tg) {
-    for (int i = 0; i < p2.n_targets; ++i)
-      if (same(p2.targets[i], tg)) return i;
-    if (p2.n_targets >= MI355Q_MAX_TARGETS) return -1;
-    p2.targets[p2.n_targets] = tg;
-    return p2.n_targets++;
-  };
-  for (int t = 0; t < plan->n_targets; ++t) {
-    mi355q_target tg = plan->targets[t];
-    lit_of[t] = 0;
-    cnt_t2[t] = -1;
-    if (tg.agg != MI355Q_PROJECT_KEY && tg.table == 0 && tg.col >= nc && tg.col < nc + nx) {
-      const int k = tg.col - nc;
-      if (src_col[k] >= 0) {
-        tg.col = src_col[k];
-        lit_of[t] = shift[k];
-      } else {
-        tg.col = new_col[k];
-      }
-    }
-    if (tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF) tg.cond.col = moved(tg.cond.col);
-    t2_of[t] = tg.agg == MI355Q_PROJECT_KEY ? (p2.n_targets < MI355Q_MAX_TARGETS ? (p2.targets[p2.n_targets] = tg, p2.n_targets++) : -1)
-                                            : add_target(tg);
-    if (t2_of[t] < 0) return kNotTaken;
-  }
-  for (int t = 0; t < plan->n_targets; ++t) {  // the counts the shifted MIN / MAX / SUM targets need
-    const mi355q_target& tg = plan->targets[t];
-    if (!lit_of[t] || tg.agg == MI355Q_COUNT || tg.agg == MI355Q_AVG) continue;  // (AVG carries its own count)
-    mi355q_target cnt{};
-    cnt.agg = MI355Q_COUNT;
-    cnt.col = p2.targets[t2_of[t]].col;
-    cnt.table = 0;
-    cnt_t2[t] = add_target(cnt);
-    if (cnt_t2[t] < 0) return kNotTaken;
-  }
-  mi355q_qmd q, q2;
-  if (qmd_init(*plan, &q) != MI355Q_OK || qmd_init(p2, &q2) != MI355Q_OK) return kNotTaken;
-  if (q.slot_width != 8 || q2.slot_width != 8 || q.output_columnar || q2.output_columnar || q.desc_type != q2.desc_type ||
-      q.entry_count != q2.entry_count || q.desc_type == MI355Q_NON_GROUPED_AGGREGATE ||
-      (q.desc_type == MI355Q_GROUP_BY_BASELINE_HASH && q.key_width != q2.key_width))
-    return kNotTaken;
-  int32_t src[MI355Q_MAX_SLOTS], dst[MI355Q_MAX_SLOTS], kind[MI355Q_MAX_SLOTS], cnt_src[MI355Q_MAX_SLOTS];
-  int64_t lit[MI355Q_MAX_SLOTS];
-  int n = 0;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const int sf = q.target_slot[t], ss = q2.target_slot[t2_of[t]];
-    if ((sf < 0) != (ss < 0)) return kNotTaken;  // (a projection read from the key columns on both sides)
-    if (sf < 0) continue;
-    const int agg = plan->targets[t].agg;
-    for (int j = 0; j < (agg == MI355Q_AVG ? 2 : 1); ++j) {
-      if (q.init_vals[sf + j] != q2.init_vals[ss + j] || n >= MI355Q_MAX_SLOTS) return kNotTaken;
-      src[n] = ss + j;
-      dst[n] = sf + j;
-      kind[n] = 0;
-      cnt_src[n] = 0;
-      lit[n] = 0;
-      if (lit_of[t] && j == 0 && agg != MI355Q_COUNT) {
-        kind[n] = (agg == MI355Q_SUM || agg == MI355Q_AVG) ? 2 : 1;
-        cnt_src[n] = agg == MI355Q_AVG ? ss + 1 : q2.target_slot[cnt_t2[t]];
-        if (cnt_src[n] < 0) return kNotTaken;
-        lit[n] = lit_of[t];
-      }
-      ++n;
-    }
-  }
-  mi355q_exec_options o2 = o;
-  o2.out_buffer = nullptr;
-  if (reserved) {
-    route_note("aggregates of column + literal from the column's aggregates + k_zip_targets");
-    return execute_impl(&p2, in, &o2, out, report, nullptr, reserved);
-  }
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-  o2.stream = s;
-  mi355q_result* r2 = nullptr;
-  mi355q_exec_report rep2{};
-  if (int32_t e2 = mi355q_execute(&p2, in, &o2, &r2, &rep2)) {
-    if (e2 == MI355Q_ERR_UNSUPPORTED || e2 == MI355Q_ERR_OUT_OF_GPU_MEM) return kNotTaken;
-    return e2;  // (out of slots included: the derived table has the stated table's entry count)
-  }
-  struct R2Guard {
-    mi355q_result* r;
-    ~R2Guard() { if (r) mi355q_result_free(r); }
-  } r2g{r2};
-  if (r2->qmd.desc_type != q.desc_type || r2->qmd.entry_count != q.entry_count || r2->qmd.slot_width != 8 ||
-      r2->qmd.output_columnar)
-    return kNotTaken;
-  for (int t = 0; t < plan->n_targets; ++t)
-    if (r2->qmd.target_slot[t2_of[t]] != q2.target_slot[t2_of[t]]) return kNotTaken;
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  DevWord err;
-  HIP_TRY(hipMalloc(&err.p, 64));
-  HIP_TRY(hipMemsetAsync(err.p, 0, 64, s));
-  HIP_TRY(launch_zip_targets(res->dplan, r2->dplan, r2->qmd.idx_target_as_key, r2->buf, res->buf, src, dst, n, (int32_t*)err.p, s,
-                             kind, cnt_src, lit, /*into_empty_table=*/true));
-  if (ev1) HIP_TRY(hipEventRecord(ev1, s));
-  int32_t h_err = 0;
-  HIP_TRY(hipMemcpyAsync(&h_err, err.p, sizeof(h_err), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (h_err) return h_err;
-  if (report) {
-    *report = rep2;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->n_launches = rep2.n_launches + 1;
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  rg.r = nullptr;
-  *out = res;
-  return MI355Q_OK;
-}
-
-// Plans with projected expressions (mi355q_expr): scan / filter / PROJECT.  The expressions of a pass of
-// fragments are evaluated into dense temporary columns (k_project), the step runs on the lowered plan — where
-// those columns are ordinary inputs, so every kernel family applies — and the passes' results are folded with
-// the reduce rule (ResultSetStorage::reduce, as for the reference's per-fragment kernels).  One pass when the
-// temporary columns fit a third of the free memory (<= 16 GB).
-int32_t execute_projected(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
-                          mi355q_result** out, mi355q_exec_report* report) {
-  mi355q_plan lp;
-  DevExprSet xs;
-  if (int32_t e = lower_exprs(*plan, &lp, &xs, true)) return e;
-  mi355q_qmd q;
-  if (int32_t e = qmd_init(*plan, &q)) return e;
-  DevPlan d;
-  if (int32_t e = build_dev_plan(lp, q, &d)) return e;
-  if (int32_t e = attach_join(lp, in, &d)) return e;
-  const int nf = in->n_frags, nc = plan->n_cols, nx = plan->n_exprs, nc2 = nc + nx;
-  if (nf == 0) return mi355q_execute(&lp, in, &o, out, report);
-  const uint32_t qual_expr_mask = expr_qual_mask(*plan);
-  int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
-  int64_t row_bytes = 0;
-  for (int k = 0; k < nx; ++k) row_bytes += plain_width(xs.e[k].store_type);
-
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  const int n_cus = cu_count_of(in->device_id);
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  const int64_t budget = std::min<int64_t>((int64_t)16 << 30, ((int64_t)free_b + ctx.proj_bytes) / 3);
-  // every (fragment, expression) chunk starts on a 16-byte boundary: the fast families want aligned columns
-  const int64_t pad = 16 * (int64_t)nx;
-  int64_t pass_rows = std::max<int64_t>(budget / std::max<int64_t>(row_bytes, 1), max_frag_rows);
-  if (o.pass_rows > 0) pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);  // tests: several passes
-  if (pass_rows > total_rows) pass_rows = total_rows;
-  const int64_t tab_bytes = ((int64_t)sizeof(void*) * nf * nc2 + 255) & ~255ll;
-  const int64_t rows_bytes = ((int64_t)sizeof(int64_t) * nf + 255) & ~255ll;
-  // (worst case: every fragment of a pass pads every expression chunk once)
-  const int64_t col_region = ((pass_rows * row_bytes + pad * nf) + 255) & ~255ll;
-  const int64_t xs_bytes = ((int64_t)sizeof(DevExprSet) + 255) & ~255ll;  // the lowered programs, read by k_project from device memory
-  const int64_t need = col_region + tab_bytes + rows_bytes + 256 + xs_bytes;
-  if (ctx.proj_bytes < need) {
-    if (ctx.proj) (void)hipFree(ctx.proj);
-    ctx.proj = nullptr;
-    ctx.proj_bytes = 0;
-    hipError_t he = hipMalloc(&ctx.proj, (size_t)need);
-    if (he != hipSuccess) {
-      last_hip_error = he;
-      (void)hipGetLastError();
-      return MI355Q_ERR_OUT_OF_GPU_MEM;
-    }
-    ctx.proj_bytes = need;
-  }
-  char* base = (char*)ctx.proj;
-  const int8_t** d_tab = (const int8_t**)(base + col_region);
-  int64_t* d_rows = (int64_t*)(base + col_region + tab_bytes);
-  int32_t* d_err = (int32_t*)(base + col_region + tab_bytes + rows_bytes);
-  DevExprSet* d_xs = (DevExprSet*)(base + col_region + tab_bytes + rows_bytes + 256);
-  HIP_TRY(hipMemsetAsync(d_err, 0, 64, s));
-  HIP_TRY(hipMemcpyAsync(d_rows, in->num_rows, sizeof(int64_t) * (size_t)nf, hipMemcpyHostToDevice, s));
-
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-
-  std::vector<const void*> cols2((size_t)nf * nc2);
-  mi355q_result* res = nullptr;
-  struct ResGuard {
-    mi355q_result*& r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  mi355q_exec_report acc{};
-  int pass = 0, f = 0;
-  while (f < nf) {
-    int f1 = f;
-    int64_t rows = 0, off = 0;
-    while (f1 < nf && (f1 == f || rows + in->num_rows[f1] <= pass_rows)) {
-      for (int c = 0; c < nc; ++c) cols2[(size_t)(f1 - f) * nc2 + c] = in->col_buffers[(size_t)f1 * nc + c];
-      for (int k = 0; k < nx; ++k) {
-        cols2[(size_t)(f1 - f) * nc2 + nc + k] = base + off;
-        off += (in->num_rows[f1] * plain_width(xs.e[k].store_type) + 15) & ~15ll;
-      }
-      rows += in->num_rows[f1];
-      ++f1;
-    }
-    if (off > col_region) return MI355Q_ERR_OUT_OF_GPU_MEM;  // (cannot happen: the region is sized for it)
-    const int pnf = f1 - f;
-    HIP_TRY(hipMemcpyAsync(d_tab, cols2.data(), sizeof(void*) * (size_t)pnf * nc2, hipMemcpyHostToDevice, s));
-    // one-operation expressions over aligned plain columns: the vectorised members (k_project_simple); an overflow there
-    // only raises word 2 and the interpreter (which knows whether the offending row counts) runs after all
-    bool simple = project_simple_shapes(xs) && !o.force_generic;
-    for (size_t i = 0; simple && i < (size_t)pnf * nc2; ++i) simple = ((uintptr_t)cols2[i] & 15) == 0;
-    HIP_TRY(launch_project(xs, d_xs, d, qual_expr_mask, d_tab, d_rows + f, pnf, max_frag_rows, d_err, n_cus, s, simple));
-    int32_t h_err3[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_err3, d_err, sizeof(h_err3), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (cols2 is re-used by the next pass; the step below synchronises anyway)
-    if (simple && h_err3[2]) {
-      HIP_TRY(hipMemsetAsync(d_err, 0, 64, s));
-      HIP_TRY(launch_project(xs, d_xs, d, qual_expr_mask, d_tab, d_rows + f, pnf, max_frag_rows, d_err, n_cus, s, false));
-      HIP_TRY(hipMemcpyAsync(h_err3, d_err, sizeof(h_err3), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-    }
-    const int32_t h_err = h_err3[0];
-    if (h_err) return h_err;
-    mi355q_inputs in2 = *in;
-    in2.n_frags = pnf;
-    in2.col_buffers = cols2.data();
-    in2.num_rows = in->num_rows + f;
-    mi355q_exec_options o2 = o;
-    o2.stream = s;
-    o2.out_buffer = pass == 0 ? o.out_buffer : nullptr;
-    mi355q_result* r2 = nullptr;
-    mi355q_exec_report rep2{};
-    if (int32_t e2 = mi355q_execute(&lp, &in2, &o2, &r2, &rep2)) return e2;
-    if (pass == 0) {
-      res = r2;
-      std::snprintf(acc.kernel_name, sizeof(acc.kernel_name), "%s", rep2.kernel_name);
-      acc.variant = rep2.variant;
-    } else {
-      const int32_t er = mi355q_result_reduce(res, r2, s);
-      mi355q_result_free(r2);
-      if (er) return er;
-    }
-    acc.kernel_ms += rep2.kernel_ms;
-    acc.n_launches += rep2.n_launches;
-    acc.spilled_rows += rep2.spilled_rows;
-    f = f1;
-    ++pass;
-  }
-  if (ev1) {
-    HIP_TRY(hipEventRecord(ev1, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (report) {
-    *report = acc;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  *out = res;
-  res = nullptr;
-  return MI355Q_OK;
-}
-
-
-// A filter compiled at plan time whose atoms include PROGRAMS (boolfilter.h, regprog.h: `b <> 0 AND a / b > 3`, `x + y > 100`,
-// `a < b`, DOUBLE leaves): the pre-pass k_filter_mask streams the filter's columns once and leaves one byte per row, the step
-// proper is `rest` (the stated plan without quals and expressions) with ONE more column — the mask, INT8 NOT NULL in [0, 1] —
-// and the qual `mask = 1`, which every typed family loads as one 4-byte word per quad.  Errors (7 / 1) surface from the
-// pre-pass: every row evaluates the filter's expressions, as the row function does ahead of its quals.
-// kNotTaken: unaligned filter columns, no room for one more column (the caller falls through to the interpreter pass).
-int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const BoolFilterHost& bfh, const mi355q_inputs* in,
-                       const mi355q_exec_options& o, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  const int nc = rest.n_cols, nc2 = nc + 1, nf = in->n_frags;
-  if (nc2 > MI355Q_MAX_COLS || rest.n_quals != 0 || rest.n_exprs != 0) return kNotTaken;
-  mi355q_plan mp = rest;
-  mp.n_cols = nc2;
-  std::memset(&mp.cols[nc], 0, sizeof(mp.cols[nc]));
-  mp.cols[nc].type = MI355Q_INT8;
-  std::memset(&mp.col_ranges[nc], 0, sizeof(mp.col_ranges[nc]));
-  mp.col_ranges[nc].valid = 1;
-  mp.col_ranges[nc].min = 0;
-  mp.col_ranges[nc].max = 1;
-  mp.n_quals = 1;
-  std::memset(&mp.quals[0], 0, sizeof(mp.quals[0]));
-  mp.quals[0].col = nc;
-  mp.quals[0].op = MI355Q_EQ;
-  mp.quals[0].ival = 1;
-  int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
-  if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched
-    route_note("k_filter_mask (program atoms + truth table -> 1 B/row)");
-    return execute_impl(&mp, in, &o, out, report, nullptr, reserved);
-  }
-  if (nf == 0) return mi355q_execute(&mp, in, &o, out, report);
-  {
-    FragView hv{nullptr, nullptr, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
-    if (!filter_mask_eligible(bfh.bf, hv)) return kNotTaken;
-  }
-  DeviceGuard g(in->device_id);
-  if (!g.ok) return MI355Q_ERR_HIP;
-  const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
-  DeviceCtx& ctx = ctx_of(in->device_id);
-  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  // one pass of fragments = as many as the mask region holds (1 B/row: 16 GB of it cover 16 G rows)
-  size_t free_b = 0, total_b = 0;
-  (void)hipMemGetInfo(&free_b, &total_b);
-  const int64_t budget = std::min<int64_t>((int64_t)16 << 30, ((int64_t)free_b + ctx.maskws_bytes) / 3);
-  int64_t pass_rows = std::max<int64_t>(budget, max_frag_rows);
-  if (o.pass_rows > 0) pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);  // tests: several passes
-  if (pass_rows > total_rows) pass_rows = total_rows;
-  const int64_t tab_bytes = ((int64_t)sizeof(void*) * nf * nc + 255) & ~255ll;    // the pre-pass's view: the stated columns
-  const int64_t mtab_bytes = ((int64_t)sizeof(void*) * nf + 255) & ~255ll;        // per fragment: its mask chunk
-  const int64_t rows_bytes = ((int64_t)sizeof(int64_t) * nf + 255) & ~255ll;
-  const int64_t col_region = (pass_rows + 32 * (int64_t)nf + 255) & ~255ll;
-  const int64_t need = col_region + tab_bytes + mtab_bytes + rows_bytes + 256;
-  if (ctx.maskws_bytes < need) {
-    if (ctx.maskws) (void)hipFree(ctx.maskws);
-    ctx.maskws = nullptr;
-    ctx.maskws_bytes = 0;
-    hipError_t he = hipMalloc(&ctx.maskws, (size_t)need);
-    if (he != hipSuccess) {
-      last_hip_error = he;
-      (void)hipGetLastError();
-      return MI355Q_ERR_OUT_OF_GPU_MEM;
-    }
-    ctx.maskws_bytes = need;
-  }
-  if (!ctx.bf_table) HIP_TRY(hipMalloc(&ctx.bf_table, sizeof(BoolFilter)));
-  HIP_TRY(hipMemcpy(ctx.bf_table, &bfh.bf, sizeof(BoolFilter), hipMemcpyHostToDevice));  // (synchronous: out of the caller's frame)
-  char* base = (char*)ctx.maskws;
-  const int8_t** d_tab = (const int8_t**)(base + col_region);
-  int8_t** d_mtab = (int8_t**)(base + col_region + tab_bytes);
-  int64_t* d_rows = (int64_t*)(base + col_region + tab_bytes + mtab_bytes);
-  int32_t* d_err = (int32_t*)(base + col_region + tab_bytes + mtab_bytes + rows_bytes);
-  HIP_TRY(hipMemsetAsync(d_err, 0, 64, s));
-  HIP_TRY(hipMemcpyAsync(d_rows, in->num_rows, sizeof(int64_t) * (size_t)nf, hipMemcpyHostToDevice, s));
-
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (report) {
-    HIP_TRY(hipEventCreate(&ev0));
-    HIP_TRY(hipEventCreate(&ev1));
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  struct EvGuard {
-    hipEvent_t a, b;
-    ~EvGuard() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } evg{ev0, ev1};
-  std::vector<const void*> cols2((size_t)nf * nc2);
-  std::vector<void*> masks((size_t)nf);
-  mi355q_result* res = nullptr;
-  struct ResGuard {
-    mi355q_result*& r;
-    ~ResGuard() { if (r) mi355q_result_free(r); }
-  } rg{res};
-  mi355q_exec_report acc{};
-  int pass = 0, f = 0;
-  while (f < nf) {
-    int f1 = f;
-    int64_t rows = 0, off = 0;
-    while (f1 < nf && (f1 == f || rows + in->num_rows[f1] <= pass_rows)) {
-      for (int c = 0; c < nc; ++c) cols2[(size_t)(f1 - f) * nc2 + c] = in->col_buffers[(size_t)f1 * nc + c];
-      cols2[(size_t)(f1 - f) * nc2 + nc] = base + off;
-      masks[(size_t)(f1 - f)] = base + off;
-      off += filter_mask_chunk_bytes(in->num_rows[f1]);
-      rows += in->num_rows[f1];
-      ++f1;
-    }
-    if (off > col_region) return MI355Q_ERR_OUT_OF_GPU_MEM;  // (cannot happen: the region is sized for it)
-    const int pnf = f1 - f;
-    HIP_TRY(hipMemcpyAsync(d_tab, in->col_buffers + (size_t)f * nc, sizeof(void*) * (size_t)pnf * nc, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_mtab, masks.data(), sizeof(void*) * (size_t)pnf, hipMemcpyHostToDevice, s));
-    int64_t prows = 0, pmax = 0;
-    for (int i = f; i < f1; ++i) {
-      prows += in->num_rows[i];
-      pmax = std::max(pmax, in->num_rows[i]);
-    }
-    FragView fv{d_tab, d_rows + f, in->col_buffers + (size_t)f * nc, in->num_rows + f, pnf, nc, prows, pmax};
-    HIP_TRY(launch_filter_mask(bfh.bf, (const BoolFilter*)ctx.bf_table, fv, d_mtab, d_err, n_cus, s));
-    int32_t h_err = 0;
-    if (bfh.bf.any_raise) {  // (a filter that cannot raise leaves nothing to look at: the step proper is enqueued right behind)
-      HIP_TRY(hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      if (h_err) return h_err;
-    } else {
-      HIP_TRY(hipStreamSynchronize(s));  // (masks / cols2 are re-used by the next pass; the step below synchronises anyway)
-    }
-    mi355q_inputs in2 = *in;
-    in2.n_frags = pnf;
-    in2.col_buffers = cols2.data();
-    in2.num_rows = in->num_rows + f;
-    mi355q_exec_options o2 = o;
-    o2.stream = s;
-    o2.out_buffer = pass == 0 ? o.out_buffer : nullptr;
-    mi355q_result* r2 = nullptr;
-    mi355q_exec_report rep2{};
-    if (int32_t e2 = mi355q_execute(&mp, &in2, &o2, &r2, &rep2)) return e2;
-    if (pass == 0) {
-      res = r2;
-      std::snprintf(acc.kernel_name, sizeof(acc.kernel_name), "%s", rep2.kernel_name);
-      acc.variant = rep2.variant;
-    } else {
-      const int32_t er = mi355q_result_reduce(res, r2, s);
-      mi355q_result_free(r2);
-      if (er) return er;
-    }
-    acc.kernel_ms += rep2.kernel_ms;
-    acc.n_launches += rep2.n_launches + 1;
-    acc.spilled_rows += rep2.spilled_rows;
-    f = f1;
-    ++pass;
-  }
-  if (ev1) {
-    HIP_TRY(hipEventRecord(ev1, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (report) {
-    *report = acc;
-    (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  *out = res;
-  res = nullptr;
-  return MI355Q_OK;
-}
-
 }  // namespace
 
-namespace {
-// An INNER join on ONE key against a dense OneToOne perfect table (mi355q_join_table::dense) whose inner side no target reads:
-// a row has a match exactly when its key lies in [min, max] (hash_join_idx, GroupByRuntime.cpp:287-297: in range ->
-// the slot, and no slot of a dense table is -1; a NULL key matches nothing, hash_join_idx_nullable :311-318), so the step is
-// the same step WITHOUT the join and with the two range quals on the key column — a plain scan for the non-grouped
-// shapes (BASELINE cfg4, Query A on the dense dimension).  kNotTaken for everything else.
-int32_t execute_dense_join_as_filter(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
-                                     mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  const mi355q_join_table* jt = plan->join_table;
-  if (plan->join_outer_col < 0 || !jt || !jt->dense || plan->join_kind != MI355Q_JOIN_INNER || plan->n_join_cols > 1 ||
-      plan->n_exprs != 0 || plan->n_quals + 2 > MI355Q_MAX_QUALS || o.force_generic || o.kernel_variant != 0)
-    return kNotTaken;
-  for (int t = 0; t < plan->n_targets && t < MI355Q_MAX_TARGETS; ++t)
-    if (plan->targets[t].table != 0 && plan->targets[t].agg != MI355Q_PROJECT_KEY) return kNotTaken;
-  const int kc = plan->join_outer_col;
-  if (kc >= plan->n_cols || col_type_code(plan->cols[kc]) < 0) return kNotTaken;
-  const int lt = tc_logical(col_type_code(plan->cols[kc]));
-  if (lt < MI355Q_INT8 || lt > MI355Q_INT64) return kNotTaken;
-  mi355q_plan p2 = *plan;
-  p2.join_outer_col = -1;
-  p2.join_table = nullptr;
-  p2.n_join_cols = 0;
-  p2.n_inner_cols = 0;
-  p2.quals[p2.n_quals++] = mi355q_qual{kc, MI355Q_GE, jt->min_key, 0.0};
-  p2.quals[p2.n_quals++] = mi355q_qual{kc, MI355Q_LE, jt->max_key, 0.0};
-  mi355q_qmd qa, qb;   // the layout does not look at the join or at the quals: the derived step's result IS the step's
-  if (qmd_init(*plan, &qa) || qmd_init(p2, &qb) || std::memcmp(&qa, &qb, sizeof(qa)) != 0) return kNotTaken;
-  route_note("join on a dense one-to-one table = range filter on the key");
-  mi355q_inputs in2 = *in;
-  in2.inner_col_buffers = nullptr;
-  in2.inner_num_rows = 0;
-  return execute_impl(&p2, &in2, &o, out, report, nullptr, reserved);
-}
-}  // namespace
+extern "C" {
 
 // ------------------------------------------------------------------------------- execute
 int32_t mi355q_execute(const mi355q_plan* plan, const mi355q_inputs* in,
@@ -2387,10 +526,13 @@ int32_t mi355q_wait(mi355q_pending* p, mi355q_exec_report* report) {
   return code;
 }
 
-namespace {
-int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
-                     const mi355q_exec_options* opts, mi355q_result** out,
-                     mi355q_exec_report* report, mi355q_pending** pend, int64_t* reserved) {
+}  // extern "C"
+
+// reserved != nullptr: RESERVE mode — plan the step, size and allocate the per-device workspace it would use,
+// launch nothing (mi355q_reserve_workspace); the column pointers are not looked at
+int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
+                              const mi355q_exec_options* opts, mi355q_result** out,
+                              mi355q_exec_report* report, mi355q_pending** pend, int64_t* reserved) {
   if (!plan || !in || !out) return MI355Q_ERR_INVALID_PLAN;
   if (in->n_frags < 0 || (in->n_frags > 0 && (!in->col_buffers || !in->num_rows)))
     return MI355Q_ERR_INVALID_PLAN;
@@ -2672,10 +814,7 @@ int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
 
   mi355q_result* res = nullptr;
   if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { mi355q_result_free(r); }
-  } rg{res};
+  ResultPtr owned(res);
 
   // device copies of the fragment tables + error word, one allocation
   const int nf = in->n_frags, nc = plan->n_cols;
@@ -3094,7 +1233,7 @@ int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
     p->device_id = in->device_id;
     ctx.inflight = p;
     *pend = p;
-    rg.r = nullptr;
+    (void)owned.release();
     *out = res;
     return MI355Q_OK;
   }
@@ -3103,15 +1242,13 @@ int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
   delete tail;
   tr.mark("synchronized");
   if (code == kRetryNoIdx) {
-    mi355q_result_free(res);
-    rg.r = nullptr;
+    owned.reset();
     mi355q_exec_options o2 = o;
     o2.flags |= MI355Q_OPT_NO_IDX_PART;
     return execute_impl(plan, in, &o2, out, report, nullptr, nullptr);
   }
   if (code == kRetryNoLds) {
-    mi355q_result_free(res);
-    rg.r = nullptr;
+    owned.reset();
     mi355q_exec_options o2 = o;
     // small replicas did not hold the groups: the largest replica next, then eight windows of it, then another family
     // (skipping the windows over large inputs was measured and is worse: with <= 65536 entries the families behind them
@@ -3123,11 +1260,12 @@ int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
     return execute_impl(plan, in, &o2, out, report, nullptr, nullptr);
   }
   if (code) return code;
-  rg.r = nullptr;
+  (void)owned.release();
   *out = res;
   return MI355Q_OK;
 }
-}  // namespace
+
+extern "C" {
 
 // ------------------------------------------------------------------------------- synth
 int32_t mi355q_generate_column(int32_t device_id, void* dst, int64_t n_rows, int64_t row_offset,
@@ -3146,3 +1284,11 @@ int32_t mi355q_generate_column(int32_t device_id, void* dst, int64_t n_rows, int
 }
 
 }  // extern "C"
+
+#if defined(HOSTSIM_DEVICE_CODE) && !defined(MI355Q_ROUTES_OWN_UNIT)
+// Only for a host-simulation recipe written before api_routes.cpp existed (the tests/helpers.py of an older commit, run
+// against this tree): its source list names api.cpp alone, so the routes join this unit there and the library still
+// links.  Every current build — the device build (heavydb_amd/_build.py SOURCES) and this tree's hostsim_lib, which
+// defines MI355Q_ROUTES_OWN_UNIT — compiles api_routes.cpp as a translation unit of its own.
+#include "api_routes.cpp"
+#endif

@@ -1,9 +1,11 @@
-// api_internal.h — what the translation units of the C-ABI share (api.cpp, api_projection.cpp): the opaque handle
-// types, the per-device workspace, and the small host-side helpers.  Internal to libmi355q.
+// api_internal.h — what the translation units of the C-ABI share (api.cpp, api_routes.cpp, api_projection.cpp,
+// api_result.cpp, api_join.cpp): the opaque handle types, the per-device workspace, and the small host-side helpers.
+// Internal to libmi355q.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -61,6 +63,7 @@ struct mi355q_result {
 };
 
 namespace mq {
+struct BoolFilterHost;  // boolfilter.h
 namespace api {
 
 // mi355q_explain: the route of a step, written down while execute_impl plans it in RESERVE mode (nothing is launched,
@@ -140,6 +143,12 @@ struct DeviceCtx {
 DeviceCtx& ctx_of(int dev);
 
 
+// an owned result handle: freed with mi355q_result_free unless released to the caller
+struct ResultFree {
+  void operator()(mi355q_result* r) const { mi355q_result_free(r); }
+};
+using ResultPtr = std::unique_ptr<mi355q_result, ResultFree>;
+
 // Small pinned-free device scratch for the error word / counters, one per call.
 struct DevWord {
   void* p = nullptr;
@@ -152,11 +161,108 @@ struct DevWord {
 int32_t result_create_impl(const mi355q_qmd* qmd, int32_t device_id, void* device_buffer, mi355q_result** out);
 // column bytes a plan must read (mi355q_exec_report.algorithmic_bytes)
 int64_t algorithmic_bytes(const mi355q_plan& p, const mi355q_inputs& in);
+
+// What every derived-plan route (api_routes.cpp) holds from its eligibility checks to its return: the device, the
+// device context under its lock, the launch stream (the caller's, else the library's own) and, once begin_timing has
+// run for a call that wants a report, the event pair around the route's work.  `status` is what construction met.
+struct RouteScope {
+  DeviceGuard dev;
+  DeviceCtx& ctx;
+  std::lock_guard<std::recursive_mutex> lock;
+  hipStream_t s = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int32_t status = MI355Q_OK;
+  RouteScope(int32_t device_id, void* stream) : dev(device_id), ctx(ctx_of(device_id)), lock(ctx.mu) {
+    status = dev.ok ? pick_stream((hipStream_t)stream) : MI355Q_ERR_HIP;
+  }
+  RouteScope(const RouteScope&) = delete;
+  ~RouteScope() {
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+  // the timed span starts here (every route has its own place for it: behind its workspace set-up)
+  int32_t begin_timing(const mi355q_exec_report* report) {
+    if (!report) return MI355Q_OK;
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
+    HIP_TRY(hipEventRecord(ev0, s));
+    return MI355Q_OK;
+  }
+  // The common tail: ev1, the route's device error word (d_err != null: read back behind ev1 and returned when set),
+  // the synchronisation, the report = acc + extra_launches with the stated plan's figures.
+  int32_t finish(mi355q_exec_report* report, const mi355q_exec_report& acc, int32_t extra_launches, const mi355q_plan& plan,
+                 const mi355q_inputs& in, int64_t total_rows, const int32_t* d_err = nullptr) {
+    return tail(report, acc, extra_launches, plan, in, total_rows, d_err, /*always_sync=*/true);
+  }
+  // The same tail for the projection and mask routes, which read no error word here and leave an UNTIMED call
+  // unsynchronised (their last inner step has synchronised the stream); every other route synchronises always.
+  int32_t finish_sync_if_timed(mi355q_exec_report* report, const mi355q_exec_report& acc, const mi355q_plan& plan,
+                               const mi355q_inputs& in, int64_t total_rows) {
+    return tail(report, acc, 0, plan, in, total_rows, nullptr, /*always_sync=*/false);
+  }
+
+ private:
+  int32_t tail(mi355q_exec_report* report, const mi355q_exec_report& acc, int32_t extra_launches, const mi355q_plan& plan,
+               const mi355q_inputs& in, int64_t total_rows, const int32_t* d_err, bool always_sync) {
+    if (ev1) HIP_TRY(hipEventRecord(ev1, s));
+    int32_t h_err = 0;
+    if (d_err) HIP_TRY(hipMemcpyAsync(&h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
+    if (ev1 || d_err || always_sync) HIP_TRY(hipStreamSynchronize(s));
+    if (h_err) return h_err;
+    if (report) {
+      *report = acc;
+      (void)hipEventElapsedTime(&report->total_ms, ev0, ev1);
+      report->n_launches = acc.n_launches + extra_launches;
+      report->rows_scanned = total_rows;
+      report->algorithmic_bytes = algorithmic_bytes(plan, in);
+    }
+    return MI355Q_OK;
+  }
+  int32_t pick_stream(hipStream_t callers) {
+    s = callers;
+    if (!s) {
+      if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
+      s = ctx.stream;
+    }
+    return MI355Q_OK;
+  }
+};
+
+constexpr int32_t kNotTaken = INT32_MIN + 7;           // internal: "use the ordinary path"
+constexpr int64_t kIdxPartMinRows = (int64_t)8 << 20;  // below this the row kernel / LDS members are as good
+
+// the step executor (api.cpp).  reserved != null: RESERVE mode, plan only; pend != null: mi355q_execute_async
+int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options* opts, mi355q_result** out,
+                     mi355q_exec_report* report, mi355q_pending** pend, int64_t* reserved = nullptr);
+// ---- the derived-plan routes (api_routes.cpp), in execute_impl's order of asking.  Each rewrites the stated plan into a
+// simpler one, runs that through mi355q_execute and fixes the result up; kNotTaken when the shape does not call for it.
+int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const BoolFilterHost& bfh, const mi355q_inputs* in,
+                       const mi355q_exec_options& o, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_shifted_args(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                             mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_cast_key(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                         mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_projected(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                          mi355q_result** out, mi355q_exec_report* report);
+int32_t execute_dense_join_as_filter(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                                     mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                            const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_perfect_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                             int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_affine_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                            int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_packed_multi(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                             const mi355q_qmd& q, const DevPlan& d, int n_cus, mi355q_result** out,
+                             mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_multi_value(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                            const mi355q_qmd& q, const DevPlan& d, mi355q_result** out, mi355q_exec_report* report,
+                            int64_t* reserved);
 // the Projection family's step (api_projection.cpp); reserved != null: plan only
 int32_t execute_projection(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
                            mi355q_exec_report* report, int64_t* reserved);
-// result accessors of a Projection buffer
-// ---- shared between api.cpp (the step executor), api_result.cpp (result objects, shards) and api_join.cpp
+// ---- shared between api.cpp (the step executor), api_routes.cpp (the derived-plan routes), api_result.cpp (result
+// objects, shards) and api_join.cpp
 RowInit make_row_init(const mi355q_qmd& q);
 ColLayout col_layout_of(const mi355q_qmd& q);
 // the device operations that walk rows run on a row-wise twin of a columnar buffer (same entries, same values)

@@ -162,10 +162,7 @@ int32_t execute_projection(const mi355q_plan* plan, const mi355q_inputs* in, con
 
   mi355q_result* res = nullptr;
   if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  struct ResGuard {
-    mi355q_result* r;
-    ~ResGuard() { mi355q_result_free(r); }
-  } rg{res};
+  ResultPtr owned(res);
 
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   LaunchStats st;
@@ -213,7 +210,7 @@ int32_t execute_projection(const mi355q_plan* plan, const mi355q_inputs* in, con
     return -(int32_t)(total > kMaxReported ? kMaxReported : total);
   }
   res->total_matched = total;
-  rg.r = nullptr;
+  (void)owned.release();
   *out = res;
   return MI355Q_OK;
 }

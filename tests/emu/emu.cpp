@@ -92,7 +92,7 @@ extern "C" int32_t emu_execute(const mi355q_plan* plan, const mi355q_inputs* in,
                                int64_t join_max, int64_t join_entries, int join_n_keys,
                                int join_width, int64_t* out, mi355q_qmd* out_qmd) {
   if (plan->n_exprs != 0) {
-    // like mi355q_execute (api.cpp execute_projected + kernels_generic.hip k_project): the expressions are
+    // like mi355q_execute (api_routes.cpp execute_projected + kernels_generic.hip k_project): the expressions are
     // evaluated into dense temporary columns and the step runs on the lowered plan
     mi355q_plan lp;
     DevExprSet xs;

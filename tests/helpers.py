@@ -341,7 +341,7 @@ _hostsim = {}
 
 
 def hostsim_lib(real_fast: bool = False) -> str:
-    """tests/hostsim: the library's host code (api.cpp, plan.cpp) and kernels_generic.hip compiled for the CPU against
+    """tests/hostsim: the library's host code (api.cpp, api_routes.cpp, plan.cpp) and kernels_generic.hip compiled for the CPU against
     a stand-in HIP runtime (memory = host memory poisoned with 0xA5, launches on a pool of host threads), the fast
     kernel families replaced by row-function stand-ins (tests/hostsim/kernels_host.cpp).  Returns the path of the
     built library (same C ABI as libmi355q.so).
@@ -365,7 +365,7 @@ def hostsim_lib(real_fast: bool = False) -> str:
     real_srcs = ["kernels_fast.hip", "kernels_lds.hip", "kernels_part.hip", "kernels_sort.hip", "kernels_idx.hip", "fast_common.h", "lds_args.h"] if real_fast else []
     deps = [os.path.join(src_dir, f) for f in ("hip_host.cpp", "kernels_host.cpp", "shim/hip/hip_runtime.h",
                                                "shim/hip/hip_runtime_api.h")] + \
-        [os.path.join(csrc, f) for f in ["api.cpp", "api_projection.cpp", "api_result.cpp", "api_join.cpp", "api_internal.h", "boolfilter.cpp", "boolfilter.h", "plan.cpp", "kernels_generic.hip",
+        [os.path.join(csrc, f) for f in ["api.cpp", "api_routes.cpp", "api_projection.cpp", "api_result.cpp", "api_join.cpp", "api_internal.h", "boolfilter.cpp", "boolfilter.h", "plan.cpp", "kernels_generic.hip",
                                          "kernels_proj.hip", "kernels_filter.hip", "regprog.h", "kernels.h", "rowfunc.h", "dev_common.h", "plan.h", "expr.h",
                                          "fast_common.h"] + real_srcs] + \
         [os.path.join(ROOT, "include", "mi355q.h"), os.path.abspath(__file__)]   # (the build recipe patches the sources)
@@ -401,7 +401,7 @@ def hostsim_lib(real_fast: bool = False) -> str:
             f.write("".join(f'    "{n}",\n' for n in names))
         with open(os.path.join(out_dir, "plain_kernels.inc"), "w") as f:
             f.write("".join(f'    "{n}",\n' for n in plain))
-        flags = ["-std=c++17", "-O1", "-g", "-fPIC", "-pthread", "-w", "-DHOSTSIM_DEVICE_CODE", "-I" + os.path.join(src_dir, "shim"), "-I" + csrc,
+        flags = ["-std=c++17", "-O1", "-g", "-fPIC", "-pthread", "-w", "-DHOSTSIM_DEVICE_CODE", "-DMI355Q_ROUTES_OWN_UNIT", "-I" + os.path.join(src_dir, "shim"), "-I" + csrc,
                  "-I" + os.path.join(ROOT, "include"), "-I" + out_dir]
         if san:
             flags += ["-fsanitize=" + san, "-fno-omit-frame-pointer", "-shared-libsan"]
@@ -418,7 +418,7 @@ def hostsim_lib(real_fast: bool = False) -> str:
         kf_cpp = os.path.join(out_dir, "kernels_filter_host.cpp")
         with open(kf_cpp, "w") as f:
             f.write(kf_src)
-        srcs = [os.path.join(csrc, "api.cpp"), os.path.join(csrc, "api_projection.cpp"), os.path.join(csrc, "api_result.cpp"),
+        srcs = [os.path.join(csrc, "api.cpp"), os.path.join(csrc, "api_routes.cpp"), os.path.join(csrc, "api_projection.cpp"), os.path.join(csrc, "api_result.cpp"),
                 os.path.join(csrc, "api_join.cpp"), os.path.join(csrc, "boolfilter.cpp"),
                 os.path.join(csrc, "plan.cpp"), kg_cpp,
                 kp_cpp, kf_cpp, os.path.join(src_dir, "kernels_host.cpp"), os.path.join(src_dir, "hip_host.cpp")]

@@ -1,4 +1,4 @@
-"""The library's HOST code on the CPU: api.cpp (route selection, derived plans, retries, workspaces, result layouts),
+"""The library's HOST code on the CPU: api.cpp / api_routes.cpp (route selection, derived plans, retries, workspaces, result layouts),
 plan.cpp and the kernels of kernels_generic.hip run here against a stand-in HIP runtime (tests/hostsim: "device"
 memory is host memory poisoned with 0xA5, a launch runs the kernel block by block on a pool of host threads with
 working barriers / shuffles / atomics); the fast kernel families are replaced by row-function stand-ins that keep
@@ -125,7 +125,7 @@ def test_case_matrix_row_kernel_only(sim, oracle, case):
 
 
 # ---- the reference's benchmark queries (tools/refbench.py): projected keys / arguments, several value columns, packed
-# 4-byte-width keys — the derived-plan routes of api.cpp, forced with kernel_variant 2 on a small table
+# 4-byte-width keys — the derived-plan routes of api_routes.cpp, forced with kernel_variant 2 on a small table
 import sys  # noqa: E402
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import refbench  # noqa: E402

@@ -206,7 +206,7 @@ def test_keyed_probe_in_several_passes(torch_cuda, oracle, monkeypatch):
 @pytest.mark.parametrize("left", [False, True], ids=["inner", "left"])
 def test_grouped_join_through_the_gather_route_at_16m_rows(torch_cuda, oracle, left, sparse):
     """SELECT f.g, COUNT(*), SUM(d.w), MAX(d.x), AVG(d.x), SUM(f.v) FROM f [LEFT] JOIN d ON f.k = d.k GROUP BY f.g over 16 M outer rows:
-    the planner's own choice (api.cpp execute_join_gather: k_join_gather + the step without a join) against the oracle's join loop
+    the planner's own choice (api_routes.cpp execute_join_gather: k_join_gather + the step without a join) against the oracle's join loop
     and against the row kernel (kernel_variant 1).  Keys that miss, NULL join keys, a nullable inner column."""
     from heavydb_amd.executor import (Executor, ExpressionRange, FetchResult, HashJoin, InputColDescriptor,
                                       RelAlgExecutionUnit, TargetExpr)

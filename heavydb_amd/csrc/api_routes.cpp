@@ -1090,8 +1090,12 @@ int32_t execute_cast_key(const mi355q_plan* plan, const mi355q_inputs* in, const
   Emission em;
   if (int32_t e = em.create(q, in->device_id, o.out_buffer, s)) return e;
   // (NULL keys of a nullable column sit at max + 1: groupByColumnCodegen translate_null_val, as plan.cpp build_dev_plan)
+  // every integer of [-2^53, 2^53] is an exact double: a DOUBLE cast of a column inside that range keeps distinct keys distinct
+  // (one entry per row of the stated table, plain stores); beyond it, and for FLOAT, entries merge and the emission uses atomics
+  const int64_t kExactDouble = (int64_t)1 << 53;
+  const bool injective = to == MI355Q_DOUBLE && cr.min >= -kExactDouble && cr.max <= kExactDouble;
   HIP_TRY(launch_cast_key_emit(em.res->dplan, r2->dplan, r2->qmd.idx_target_as_key, to == MI355Q_FLOAT ? 1 : 0, cd.nullable != 0,
-                               q2.group_min[0], q2.group_null_key[0], r2->buf, em.res->buf, em.d_err(), s));
+                               injective ? 1 : 0, q2.group_min[0], q2.group_null_key[0], r2->buf, em.res->buf, em.d_err(), s));
   if (int32_t e = rs.finish(report, rep2, 1, *plan, *in, total_rows, em.d_err())) return e;
   *out = em.res.release();
   return MI355Q_OK;

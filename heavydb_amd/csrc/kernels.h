@@ -140,7 +140,7 @@ hipError_t launch_affine_twin_emit(const DevPlan& pf, const DevPlan& ps, int idx
                                    const int64_t* base, const int64_t* stride, const int64_t* sub, int64_t* fin, int32_t* d_err,
                                    hipStream_t s);
 // GROUP BY CAST(int column AS DOUBLE | FLOAT): entries of the integer-keyed perfect table re-keyed and merged into the baseline table
-hipError_t launch_cast_key_emit(const DevPlan& pf, const DevPlan& ps, int idx_key_s, int cast_to_float, int translate,
+hipError_t launch_cast_key_emit(const DevPlan& pf, const DevPlan& ps, int idx_key_s, int cast_to_float, int translate, int injective,
                                 int64_t key_min, int64_t null_key, const int64_t* sub, int64_t* fin, int32_t* d_err,
                                 hipStream_t s);
 // (kind / cnt_src / lit: per copy, the `aggregate of column + literal` fix-up of ZipMap; null = plain copies)

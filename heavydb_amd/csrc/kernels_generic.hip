@@ -934,7 +934,7 @@ struct CastKeyArgs {
   int32_t idx_key_s;      // keyless integer-keyed table: the target whose slot tells an empty entry
   int32_t cast_to_float;  // the cast's type: FLOAT (else DOUBLE)
   int32_t translate;      // the integer column is nullable: its NULL sits at `null_key` (max + 1)
-  int32_t reserved;
+  int32_t injective;      // DOUBLE cast, the column's range inside [-2^53, 2^53]: distinct integers stay distinct doubles
   int64_t key_min, null_key;
 };
 __global__ __launch_bounds__(kBlock) void k_cast_key_emit(DevPlan pf, DevPlan ps, CastKeyArgs ck,
@@ -971,10 +971,12 @@ __global__ __launch_bounds__(kBlock) void k_cast_key_emit(DevPlan pf, DevPlan ps
       }
       DevTarget lt = tf;
       lt.slot = 0;
-      // (a DOUBLE cast is injective on these keys and the table was initialised for this emission: the row belongs to this lane
-      // alone — plain read-modify-write, round 6; 10 M entries x 7 slots of global atomics were 3.1 ms; two integers may share a FLOAT)
-      if (ck.cast_to_float) reduce_target<true>(lt, pf.init_vals + tf.slot, slots_f + tf.slot, win);
-      else reduce_target<false>(lt, pf.init_vals + tf.slot, slots_f + tf.slot, win);
+      // (ck.injective — a DOUBLE cast of keys inside [-2^53, 2^53], every one an exact double — and the table was initialised for
+      // this emission: the row belongs to this lane alone — plain read-modify-write, round 6; 10 M entries x 7 slots of global
+      // atomics were 3.1 ms.  Two integers may share a FLOAT, and beyond 2^53 a DOUBLE: neighbouring lanes then merge into ONE
+      // row — atomics)
+      if (ck.injective) reduce_target<false>(lt, pf.init_vals + tf.slot, slots_f + tf.slot, win);
+      else reduce_target<true>(lt, pf.init_vals + tf.slot, slots_f + tf.slot, win);
     }
   }
 }
@@ -1677,11 +1679,11 @@ hipError_t launch_affine_twin_emit(const DevPlan& pf, const DevPlan& ps, int idx
   return hipGetLastError();
 }
 
-hipError_t launch_cast_key_emit(const DevPlan& pf, const DevPlan& ps, int idx_key_s, int cast_to_float, int translate,
+hipError_t launch_cast_key_emit(const DevPlan& pf, const DevPlan& ps, int idx_key_s, int cast_to_float, int translate, int injective,
                                 int64_t key_min, int64_t null_key, const int64_t* sub, int64_t* fin, int32_t* d_err,
                                 hipStream_t s) {
   if (ps.entry_count <= 0) return hipSuccess;
-  const CastKeyArgs ck{idx_key_s, cast_to_float, translate, 0, key_min, null_key};
+  const CastKeyArgs ck{idx_key_s, cast_to_float, translate, cast_to_float ? 0 : injective, key_min, null_key};
   hipLaunchKernelGGL(k_cast_key_emit, dim3(grid_for(ps.entry_count)), dim3(kBlock), 0, s, pf, ps, ck, sub, fin, d_err);
   return hipGetLastError();
 }

@@ -421,6 +421,25 @@ def test_cast_key_route_with_null_keys_and_float_collisions(sim, oracle):
         assert rs is not None and rs.report.n_launches >= 2, rs.report.n_launches
 
 
+@pytest.mark.parametrize("to,key_type,base,span,key_null_frac,want_groups",
+                         [(capi.DOUBLE, capi.INT64, 2**60, 2000, 0.0, 9), (capi.DOUBLE, capi.INT64, -2**60, 2000, 0.05, 18),
+                          (capi.DOUBLE, capi.INT64, 2**53 - 1000, 2000, 0.05, 1502), (capi.FLOAT, capi.INT32, 2**28, 3000, 0.05, 96)],
+                         ids=["double_2p60", "double_minus_2p60_null_keys", "double_straddling_2p53_null_keys", "float_2p28_null_keys"])
+def test_cast_key_route_with_casts_that_merge_entries(sim, oracle, to, key_type, base, span, key_null_frac, want_groups):
+    """INT64 keys beyond 2^53 round to the same DOUBLE (2 - 256 integers each), INT32 keys at 2^28 to the same FLOAT (32 each):
+    the route is kept, the entries merge through the ATOMIC reduce rule (CastKeyArgs::injective = 0 — the plain
+    read-modify-write is for DOUBLE casts of keys inside [-2^53, 2^53] only).  The shapes of tests/test_zz_gpu_emit_invariants.py,
+    which holds the device to them; here the route being taken and the merge itself are pinned without a GPU (lanes run one after
+    the other: a lost update cannot show)."""
+    from tests.test_zz_gpu_emit_invariants import _cast_key_case
+    ra, frags, groups, distinct = _cast_key_case(np.random.default_rng(53), 40_000, to, key_type, base, span, key_null_frac,
+                                                 capi.INT64, 8192)
+    assert distinct == span and groups == want_groups, (distinct, groups)
+    rs = flow._check(oracle, cases_mod.Case("cast_key_merging", ra, frags), kernel_variant=2)
+    assert rs is not None and rs.report.n_launches >= 2, rs.report.n_launches
+    assert rs.rowCount() == want_groups, rs.rowCount()
+
+
 # ---- baseline steps over several ranged INT keys: a perfect-hash twin (index-partitioned family) + k_perfect_twin_emit --------
 @pytest.mark.parametrize("name", ["PHM006", "MSPHM005", "MSPHM007"])
 def test_perfect_twin_route_on_the_benchmark_shapes(sim, oracle, name):

@@ -155,6 +155,30 @@ MQ_D void eval_exprs_lds(const DevExprSet& xs, const ProjExprLds& L, uint32_t ma
   }
 }
 
+// the workgroup's dynamic LDS (the general member's image and, behind it, the expressions' area; the one-to-many member
+// keeps the area alone)
+MQ_D char* proj_dyn_lds() {
+  extern __shared__ __attribute__((aligned(16))) char s_dyn[];
+  return s_dyn;
+}
+// the expressions' area at `base`: the programs (copied once, as XNodes), a.x_below stack levels, the expressions' values.
+// Every thread of the workgroup calls it (one barrier behind the copy)
+MQ_D void proj_expr_area(const ProjArgs& a, char* base, int tid, ProjExprLds& L) {
+  XNode* const s_prog = (XNode*)base;
+  for (int w = tid; w < a.xs->n * MI355Q_MAX_EXPR_NODES; w += kBlock) {
+    const DevExprNode& nd = a.xs->e[w / MI355Q_MAX_EXPR_NODES].nodes[w % MI355Q_MAX_EXPR_NODES];
+    XNode x;
+    x.h = nd.flags >> kExHandlerShift;
+    x.pad_ = 0;
+    x.lit = nd.ilit;
+    s_prog[w] = x;
+  }
+  L.prog = s_prog;
+  L.stk.st = (int64_t*)(s_prog + MI355Q_MAX_EXPRS * MI355Q_MAX_EXPR_NODES);
+  L.xv = L.stk.st + (size_t)a.x_below * kXJ * kBlock;
+  __syncthreads();
+}
+
 MQ_D unsigned long long wave_excl_scan_u32x2(unsigned long long v, unsigned long long* total) {
   // inclusive scan over the wave of two packed 32-bit counters
   const int lane = threadIdx.x & 63;
@@ -965,7 +989,7 @@ __global__ __launch_bounds__(kBlock, (XF || COL) ? 1 : NT <= 3 ? 4 : 3) void k_p
 // join; pass B probes again for the rows it writes and reads the inner columns through the matched row)
 template <bool HJ>
 __global__ __launch_bounds__(kBlock) void k_proj_compact_lds(DevPlan p, ProjArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char s_img[];
+  char* const s_img = proj_dyn_lds();
   __shared__ unsigned long long s_wave[kWaves];
   __shared__ long long s_bcast[2];
 
@@ -976,21 +1000,7 @@ __global__ __launch_bounds__(kBlock) void k_proj_compact_lds(DevPlan p, ProjArgs
   // the expressions' LDS area: programs (copied once), stack, values
   ProjExprLds L{};
   L.stk.tid = tid;
-  if (a.xs && a.x_lds_off >= 0) {
-    XNode* const s_prog = (XNode*)(s_img + a.x_lds_off);
-    for (int w = tid; w < a.xs->n * MI355Q_MAX_EXPR_NODES; w += kBlock) {
-      const DevExprNode& nd = a.xs->e[w / MI355Q_MAX_EXPR_NODES].nodes[w % MI355Q_MAX_EXPR_NODES];
-      XNode x;
-      x.h = nd.flags >> kExHandlerShift;
-      x.pad_ = 0;
-      x.lit = nd.ilit;
-      s_prog[w] = x;
-    }
-    L.prog = s_prog;
-    L.stk.st = (int64_t*)(s_prog + MI355Q_MAX_EXPRS * MI355Q_MAX_EXPR_NODES);
-    L.xv = L.stk.st + (size_t)a.x_below * kXJ * kBlock;
-    __syncthreads();
-  }
+  if (a.xs && a.x_lds_off >= 0) proj_expr_area(a, s_img + a.x_lds_off, tid, L);
 
   for (;;) {
     // ---- the next tile, in ticket order (a tile's predecessors have all been taken by running workgroups)
@@ -1210,7 +1220,13 @@ __global__ __launch_bounds__(kBlock) void k_proj_compact_lds(DevPlan p, ProjArgs
 // the inner columns' NULLs), the (iteration, wave) totals are scanned, the tile's total goes through the same look-back;
 // pass B probes again and every lane writes its rows' entries — a row's matches in payload order, rows in (fragment, row)
 // order, as the reference's CPU executor emits them — straight to the buffer (no LDS image: a row may have any number of
-// matches).  Plain column targets of either side; quals of any kind without expressions.
+// matches).  Column targets of either side; quals of any kind.
+// HX: the plan has expressions (targets, or read by a qual) — the evaluator's area in dynamic LDS as in k_proj_compact_lds
+// (a.x_lds_off < 0: the row-at-a-time evaluator); pass A's filter evaluates the quals' expressions, pass B evaluates all of
+// them once per outer row that writes an entry — the join loop encloses the body, so the row's value goes into each of its
+// entries and its error counts only if one of them lies below entry_count (a row the filter drops, an INNER join leaves
+// unmatched, or whose entries all lie past the scan limit / the buffer's end raises nothing).  HX = false is the member
+// of round 6 unchanged: no dynamic LDS, no evaluator.
 MQ_D JoinMatch proj_join_matches(const DevPlan& p, const int8_t* const* fc, int64_t pos) {
   int64_t jk[MI355Q_MAX_GROUP_COLS];
   bool null_key = false;
@@ -1221,14 +1237,20 @@ MQ_D JoinMatch proj_join_matches(const DevPlan& p, const int8_t* const* fc, int6
   if (null_key) return JoinMatch{nullptr, -1, 0};
   return join_lookup(p, jk);
 }
+template <bool HX>
 __global__ __launch_bounds__(kBlock) void k_proj_join_1n(DevPlan p, ProjArgs a) {
   __shared__ unsigned long long s_cnt[kIters * kWaves];  // entries of (iteration, wave); then their exclusive prefix in that order
   __shared__ long long s_bcast[2];
   const ProjSpec& ps = a.ps;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool left = p.join_kind == MI355Q_JOIN_LEFT;
+  const int n_phys = ps.n_phys_cols;
   int32_t err = 0;
   ProjExprLds L{};
+  if (HX) {
+    L.stk.tid = tid;
+    if (a.x_lds_off >= 0) proj_expr_area(a, proj_dyn_lds() + a.x_lds_off, tid, L);  // (a launch argument: uniform)
+  }
   for (;;) {
     if (tid == 0) s_bcast[0] = (long long)atomicAdd(&a.counters[0], 1ull);
     __syncthreads();
@@ -1248,7 +1270,7 @@ __global__ __launch_bounds__(kBlock) void k_proj_join_1n(DevPlan p, ProjArgs a) 
     const int8_t* const* fc = a.cols + (size_t)f * ps.n_cols_table;
     const int64_t n = a.num_rows[f];
     const int64_t row0 = (tile - a.tile_start[f]) * kTileRows;
-    const uint64_t m = tile_filter<false, false>(p, a, L, fc, n, row0, &err);  // the quals alone
+    const uint64_t m = tile_filter<HX, false>(p, a, L, fc, n, row0, &err);  // the quals alone (HX: with the expressions they read)
     // ---- pass A: entries per (iteration, wave)
 #pragma unroll 1
     for (int u = 0; u < kIters; ++u) {
@@ -1301,7 +1323,32 @@ __global__ __launch_bounds__(kBlock) void k_proj_join_1n(DevPlan p, ProjArgs a) 
         if (lane >= d) inc += o;
       }
       int64_t e = tile_base + (int64_t)s_cnt[u * kWaves + wave] + (int64_t)(inc - c);
+      if (HX && L.xv) {  // the quad's four rows together, where one of them writes an entry (a row past the fragment's end repeats the last one)
+        int64_t e_row = e;
+        uint32_t writes = 0;
+#pragma unroll
+        for (int i = 0; i < kXJ; ++i) {
+          if (jm[i].count > 0 && e_row < ps.entry_count) writes |= 1u << i;
+          e_row += jm[i].count;
+        }
+        if (writes) {
+          int64_t p4[kXJ];
+          int32_t e4[kXJ] = {0, 0, 0, 0};
+#pragma unroll
+          for (int i = 0; i < kXJ; ++i) p4[i] = r + i < n ? r + i : n - 1;
+          eval_exprs_lds(*a.xs, L, (1u << a.xs->n) - 1u, fc, p4, e4);
+#pragma unroll
+          for (int i = 0; i < kXJ; ++i)
+            if (((writes >> i) & 1u) && e4[i] && !err) err = e4[i];
+        }
+      }
       for (int i = 0; i < 4; ++i) {
+        int64_t xv[HX ? MI355Q_MAX_EXPRS : 1];
+        if (HX && !L.xv && jm[i].count > 0 && e < ps.entry_count) {  // no room in LDS: row by row, the private stack
+          int32_t e1 = 0;
+          eval_exprs(*a.xs, (1u << a.xs->n) - 1u, fc, r + i, xv, &e1);
+          if (e1 && !err) err = e1;
+        }
         for (int32_t j = 0; j < jm[i].count; ++j, ++e) {
           if (e >= ps.entry_count) break;
           const int64_t inner_pos = jm[i].ids ? (int64_t)jm[i].ids[j] : jm[i].single;
@@ -1311,6 +1358,7 @@ __global__ __launch_bounds__(kBlock) void k_proj_join_1n(DevPlan p, ProjArgs a) 
             const ProjTarget& pt = ps.t[t];
             int64_t v;
             if (pt.col >= kProjInnerCol) v = inner_pos >= 0 ? col_value_bits(p.inner_cols[pt.col - kProjInnerCol], pt.code, inner_pos) : proj_null_bits(pt.code);
+            else if (HX && pt.col >= n_phys) v = L.xv ? L.xv[(size_t)((pt.col - n_phys) * kXJ + i) * kBlock + tid] : xv[pt.col - n_phys];
             else v = col_value_bits(fc[pt.col], pt.code, r + i);
             if (pt.kind == PROJ_F32_TO_F64) v = dbl_bits((double)bits_flt((int32_t)(uint32_t)v));
             if (!ps.columnar) {
@@ -1540,11 +1588,14 @@ hipError_t launch_projection(const DevPlan& p, const ProjSpec& ps, const DevExpr
     fa.tcol_off[t] = pt.col_off;
   }
   // the LDS image of one sub-tile (general member): every row of it may match; columnar runs are padded to 8 bytes each
-  size_t lds = fast_ok ? 0 : (size_t)a.sub_iters * kIterRows * row_bytes + (ps.columnar ? 8 * (size_t)(ps.n_targets + 1) : 0);
+  // (the one-to-many member writes its entries straight to the buffer: no image, the expressions' area starts at 0)
+  const bool join_1n = p.join_col >= 0 && p.join_hash_type >= 2;
+  size_t lds = fast_ok || join_1n ? 0 : (size_t)a.sub_iters * kIterRows * row_bytes + (ps.columnar ? 8 * (size_t)(ps.n_targets + 1) : 0);
   a.x_lds_off = -1;
   a.x_below = 0;
   const int x_deepest = ps.x_info & 0xff, x_n = ps.x_info >> 8;
-  if (d_xs && !fast_ok && x_deepest > 0) {  // + the expressions' area (programs, stack below the top, values)
+  // (pass_rows -4: tests force the row-at-a-time evaluator, which programs too deep for the area beside a wide image take)
+  if (d_xs && !fast_ok && x_deepest > 0 && tune_knobs().pass_rows != -4) {  // + the expressions' area (programs, stack below the top, values)
     const size_t img = (lds + 15) & ~(size_t)15;
     const size_t xarea = (size_t)MI355Q_MAX_EXPRS * MI355Q_MAX_EXPR_NODES * sizeof(XNode) +
                          (size_t)(x_deepest - 1 + x_n) * kXJ * kBlock * 8;
@@ -1557,7 +1608,9 @@ hipError_t launch_projection(const DevPlan& p, const ProjSpec& ps, const DevExpr
   if (st) {
     st->kernel_name = "k_proj_compact";
     st->n_launches = 1;
-    st->variant = fast_ok ? 0 : a.sub_iters;
+    // 0 the fast member, 1 / 2 the general member and the plain one-to-many member (iterations per sub-tile), 16 the split
+    // route; a one-to-many join with expressions: 32 (the evaluator in LDS) / 33 (row at a time, private stack)
+    st->variant = fast_ok ? 0 : join_1n && d_xs ? (a.x_lds_off >= 0 ? 32 : 33) : a.sub_iters;
   }
   if (tiles > 0) {
     // fast member: 256 staged rows per wave
@@ -1572,9 +1625,13 @@ hipError_t launch_projection(const DevPlan& p, const ProjSpec& ps, const DevExpr
       if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)k_proj_compact_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         (void)hipFuncSetAttribute((const void*)k_proj_compact_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
+        (void)hipFuncSetAttribute((const void*)k_proj_join_1n<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048);
         attr_set = true;
       }
-      if (p.join_col >= 0 && p.join_hash_type >= 2) hipLaunchKernelGGL(k_proj_join_1n, dim3((unsigned)std::min<int64_t>(tiles, (int64_t)n_cus * 4)), dim3(kBlock), 0, s, p, a);
+      // (one-to-many: fewer workgroups may be resident than launched — a wide expressions' area —; tiles go out in ticket order)
+      const unsigned grid_1n = (unsigned)std::min<int64_t>(tiles, (int64_t)n_cus * 4);
+      if (join_1n && d_xs) hipLaunchKernelGGL(k_proj_join_1n<true>, dim3(grid_1n), dim3(kBlock), lds, s, p, a);
+      else if (join_1n) hipLaunchKernelGGL(k_proj_join_1n<false>, dim3(grid_1n), dim3(kBlock), 0, s, p, a);
       else if (p.join_col >= 0) hipLaunchKernelGGL(k_proj_compact_lds<true>, dim3((unsigned)grid), dim3(kBlock), lds, s, p, a);
       else hipLaunchKernelGGL(k_proj_compact_lds<false>, dim3((unsigned)grid), dim3(kBlock), lds, s, p, a);
     } else {

@@ -150,7 +150,11 @@ typedef enum mi355q_agg {
    * row is an entry — one per outer row over a one-to-one table, the whole matching set over a one-to-many table
    * (HashJoin::codegenMatchingSet, HashJoin.cpp:209; the entries of one outer row in the payload run's order, which
    * depends on the build order as in the reference); a LEFT join keeps an unmatched row once with the inner columns'
-   * NULLs.  MI355Q_ERR_UNSUPPORTED: a one-to-many table together with projected expressions. */
+   * NULLs.  Projected expressions (as targets, or read by a qual) go through either kind of table: the join loop encloses
+   * the row function's body, so over a one-to-many table an expression's value stands in EVERY entry of its outer row and
+   * a target expression's error (division by zero, overflow) counts once the row writes an entry below entry_count — a
+   * row the quals drop, an INNER join leaves unmatched, or whose entries all lie past the scan limit or the buffer's end
+   * raises nothing; an unmatched row of a LEFT join writes one entry, so its error counts. */
   MI355Q_PROJECT = 101
 } mi355q_agg;
 
@@ -529,7 +533,10 @@ typedef struct mi355q_exec_options {
   int32_t probe_keyed_passes;   /* keyed payload probe: passes per partition, 1..4 (tests: several passes
                                    on a small table) */
   int64_t pass_rows;            /* packed-key and projected-expression routes: rows per pass (tests force
-                                   several passes; the fragments are never split) */
+                                   several passes; the fragments are never split).  Projection steps: negative values
+                                   force a member (tests and tools): -1 the general member, -2 / -3 the fast member as
+                                   one launch / as the split route, -4 the expressions' row-at-a-time evaluator (no
+                                   LDS area: what programs too deep for the area beside a wide image take) */
   uint32_t flags;               /* MI355Q_OPT_* */
   int32_t tune_cus;             /* plan and launch as if the device had this many CUs (experiments: how a family
                                    scales with the CU count, whether two families could share the device) */
@@ -571,7 +578,9 @@ typedef struct mi355q_exec_report {
   float total_ms;       /* HIP-event time of the whole call on the launch stream */
   int32_t n_launches;   /* launches of the dominant kernel */
   int32_t variant;      /* member of the family that ran (informational; e.g. k_groupby_lds: 4 run-time roles, 5 typed;
-                           k_idx_scatter: 6 plain records, 7 / 8 the packed 4- / 2-byte word) */
+                           k_idx_scatter: 6 plain records, 7 / 8 the packed 4- / 2-byte word; k_proj_compact: 0 the fast
+                           member, 1 / 2 the general member and the one-to-many member without expressions, 16 the split
+                           route, 32 / 33 the one-to-many member with expressions — evaluator in LDS / row at a time) */
   int64_t rows_scanned;
   int64_t algorithmic_bytes; /* column bytes the plan must read */
   int64_t spilled_rows;      /* rows that took the direct-atomic spill path */

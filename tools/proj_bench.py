@@ -25,10 +25,11 @@ def main():
     ap.add_argument("--sel", default="0.01,0.5,0.99")
     ap.add_argument("--cols", default="1,3,6")
     ap.add_argument("--blocks-per-cu", type=int, default=0)
-    ap.add_argument("--variant", default="plain", choices=["plain", "general", "expr", "exprfilter", "join", "join1n"],
+    ap.add_argument("--variant", default="plain", choices=["plain", "general", "expr", "exprfilter", "join", "join1n", "join1n_expr"],
                     help="general: the same shapes through the general member (pass_rows = -1); expr: the second target is v1 * 2.0 "
                          "and a third one v0 + 1 (expressions in registers); join: SELECT v.., d.w FROM t JOIN d ON t.fk = d.k "
-                         "(d: 1 M rows, dense keys; fk = i32 >> 11)")
+                         "(d: 1 M rows, dense keys; fk = i32 >> 11); join1n: every key of d twice (a one-to-many table); join1n_expr: "
+                         "the join1n step with its first target v0 + 1 and its second CAST(fk AS DOUBLE) * 2.5")
     ap.add_argument("--route", default="auto", choices=["auto", "fused", "split"], help="the fast member as ONE launch (ticket + look-back; pass_rows -2) or as k_proj_mask + k_proj_scan_tiles + pass B (pass_rows -3); auto: split from 4 096 tiles")
     ap.add_argument("--interpreted", action="store_true", help="MI355Q_OPT_NO_COMPILED_FILTER: an expression filter through the general member's interpreter instead of the row-mask pre-pass")
     ap.add_argument("--generic-member", action="store_true", help="MI355Q_OPT_LDS_GENERIC_MEMBER: expression targets through the general member's interpreter even where they are forms of the fast member")
@@ -67,10 +68,10 @@ def main():
                     ra.exprs = [Expr.col(0).cast(capi.INT64).add(Expr.lit(capi.INT64, 5), capi.INT64).cmp(capi.EX_LT, Expr.lit(capi.INT64, k_lit + 5))
                                 .with_range(ExpressionRange(True, 0, 1, False))]
                     ra.simple_quals = [Qual(nc, capi.EQ, 1)]
-                elif args.variant in ("join", "join1n"):
+                elif args.variant in ("join", "join1n", "join1n_expr"):
                     from heavydb_amd.executor import ExpressionRange, FetchResult, HashJoin, InputColDescriptor, TargetExpr
                     m = 1 << 20
-                    one_n = args.variant == "join1n"   # every key of the dimension twice: two entries per matching outer row
+                    one_n = args.variant != "join"   # every key of the dimension twice: two entries per matching outer row
                     if "join" not in cache:
                         dk = torch.randperm(m, device="cuda").to(torch.int64)
                         if one_n:
@@ -94,6 +95,15 @@ def main():
                     info = dict(info, bytes_per_row=info["bytes_per_row"] + 4, out_bytes_per_row=info["out_bytes_per_row"] + 8)
                     if one_n:
                         ra.max_groups_buffer_entry_guess = 2 * ra.max_groups_buffer_entry_guess
+                    if args.variant == "join1n_expr":   # (the expressions are outer columns nc + 1, nc + 2: nc is the join key now)
+                        from heavydb_amd.executor import Expr
+                        tg = list(ra.target_exprs)
+                        ra.exprs = [Expr.col(1).add(Expr.lit(capi.INT64, 1), capi.INT64).with_range(ExpressionRange(True, -500_000_000, 500_000_007))]
+                        tg[0] = TargetExpr(capi.PROJECT, nc + 1)
+                        if n_out >= 2:
+                            ra.exprs.append(Expr.col(nc).cast(capi.DOUBLE).mul(Expr.lit(capi.DOUBLE, 2.5), capi.DOUBLE).with_range(ExpressionRange()))
+                            tg[1] = TargetExpr(capi.PROJECT, nc + 2)
+                        ra.target_exprs = tg
                 q = capi.QMD()
                 assert lib.mi355q_qmd_init(ctypes.byref(ra.to_plan()), ctypes.byref(q)) == 0
                 out = torch.empty(lib.mi355q_qmd_buffer_bytes(ctypes.byref(q)) // 8, dtype=torch.int64, device="cuda")

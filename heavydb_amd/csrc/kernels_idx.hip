@@ -36,6 +36,7 @@
 
 #include "fast_common.h"
 #include "lds_args.h"
+#include "part_host.h"
 
 namespace mq {
 
@@ -805,11 +806,9 @@ __global__ __launch_bounds__(256) void k_idx_spill(IdxGeom g, IdxCols c, DevPlan
 }
 
 // --------------------------------------------------------------------------------------------------------- host
-struct IdxPlanHost {
+struct IdxPlanHost : part_host::RunSizes {  // chunk_rows, rec_bytes, cnt_bytes, scratch_bytes
   IdxGeom g;
   IdxCols c;
-  int64_t chunk_rows;
-  int64_t rec_bytes, cnt_bytes, scratch_bytes;
   size_t lds1, lds2;
 };
 
@@ -923,42 +922,22 @@ bool make_idx_plan_impl(const DevPlan& p, const FragView& fv, int n_cus, int64_t
     }
   }
   if (g.R > (uint32_t)kIdxMaxSub) return false;
-  g.L = kIdxStageUnits / P;
-  g.lgL = 0;
-  while ((1u << g.lgL) < g.L) ++g.lgL;
+  part_host::line_geometry(g, kIdxStageUnits, P);
   g.B = n_cus;
-  const int recs_per_unit = 1 << g.rs;
-  int64_t chunk_rows = fv.total_rows > 0 ? fv.total_rows : 1;
-  if (chunk_rows > 0xfff00000ll) chunk_rows = 0xfff00000ll;  // 32-bit run positions / LDS counters per chunk
-  if (scratch_cap <= 0) scratch_cap = kDefaultScratchCap;
-  for (;;) {
-    const double per_run = (double)chunk_rows / ((double)P * g.B);  // records
-    uint64_t cap = (uint64_t)((per_run * 1.2 + 6.0 * __builtin_sqrt(per_run + 1.0)) / recs_per_unit) + g.L;  // units
-    cap = (cap + g.L - 1) / g.L * g.L;  // whole lines
-    const bool too_many = (uint64_t)P * g.B * cap >= ((uint64_t)1 << 31);  // 32-bit unit indices in phase 1
-    if (!too_many) {
-      // packed records: a unit's {cnt : sum of codes} word must hold every record of a partition (B runs of cap units)
-      if (g.pk && (uint64_t)g.B * cap * recs_per_unit * (uint64_t)(max_code ? max_code : 1) >= ((uint64_t)1 << 32)) return false;
-      g.cap = (uint32_t)cap;
-      h.rec_bytes = (int64_t)P * g.B * (int64_t)cap * 16;
-      h.cnt_bytes = ((int64_t)P * g.B * 4 + 255) & ~255ll;
-      int64_t spill_cap = chunk_rows / 16;
-      if (spill_cap < (int64_t)kIdxSpillMin) spill_cap = kIdxSpillMin;
-      if (spill_cap > 0x3fffffffll) spill_cap = 0x3fffffffll;
-      g.spill_cap = (uint32_t)spill_cap;
-      h.scratch_bytes = h.rec_bytes + h.cnt_bytes + 256 + spill_cap * 16;
-    }
-    if (!too_many && (h.scratch_bytes <= scratch_cap || chunk_rows <= fv.max_frag_rows)) break;
-    if (chunk_rows <= fv.max_frag_rows) return false;
-    chunk_rows = (int64_t)(chunk_rows * 0.9);
-    if (chunk_rows < fv.max_frag_rows) chunk_rows = fv.max_frag_rows;
-  }
-  if (fv.total_rows > chunk_rows) {  // equal-sized chunks
-    const int64_t n_chunks = (fv.total_rows + chunk_rows - 1) / chunk_rows;
-    const int64_t even = (fv.total_rows + n_chunks - 1) / n_chunks + fv.max_frag_rows;
-    if (even < chunk_rows) chunk_rows = even;
-  }
-  h.chunk_rows = chunk_rows;
+  part_host::RunFamily rf{};
+  rf.recs_per_unit = 1 << g.rs;
+  rf.unit_bytes = 16;
+  rf.shrink = 0.9;
+  rf.index_limit = (uint64_t)1 << 31;  // 32-bit unit indices in phase 1
+  rf.spill_min = kIdxSpillMin;
+  rf.spill_max = 0x3fffffffll;
+  rf.spill_entry_bytes = 16;
+  rf.even_chunks = true;
+  // packed records: a unit's {cnt : sum of codes} word must hold every record of a partition (B runs of cap units)
+  rf.word_weight = g.pk ? (uint64_t)rf.recs_per_unit * (uint64_t)(max_code ? max_code : 1) : 0;
+  if (!part_host::size_runs(fv.total_rows, fv.max_frag_rows, P, g.B, g.L, scratch_cap, rf, &h)) return false;
+  g.cap = h.cap;
+  g.spill_cap = h.spill_cap;
   h.lds1 = (size_t)kIdxStageUnits * 16 + (size_t)P * 12 + 32;
   h.lds2 = (size_t)g.S2 * entry_bytes + (size_t)g.B * 4 + 16;
   return h.lds1 <= 160 * 1024 && h.lds2 <= 160 * 1024;
@@ -1013,44 +992,29 @@ hipError_t idx_aggregate_pk(const IdxPlanHost& h, const DevPlan& p, const v4i32*
 template <int NK, int NV, int RS, bool PK>
 hipError_t idx_run(const IdxPlanHost& h, const DevPlan& p, const FragView& fv, int64_t* out, int32_t* d_err, void* scratch,
                    int n_cus, hipStream_t s, LaunchStats* st) {
-  v4i32* recs = (v4i32*)scratch;
-  uint32_t* cnt = (uint32_t*)((char*)scratch + h.rec_bytes);
-  char* spill_base = (char*)scratch + h.rec_bytes + h.cnt_bytes;
-  IdxSpill sl{(uint32_t*)spill_base, (v4i32*)(spill_base + 256), d_err, h.g.spill_cap};
-  hipEvent_t* ev_pool = st->ev_pool;
-  int ev_i = 0;
-  int f = 0;
-  while (f < fv.n_frags) {
-    int64_t rows = 0;
-    int f1 = f;
-    while (f1 < fv.n_frags && (f1 == f || rows + fv.h_num_rows[f1] <= h.chunk_rows)) {
-      rows += fv.h_num_rows[f1];
-      ++f1;
-    }
-    hipError_t e = hipMemsetAsync(spill_base, 0, 256, s);
+  const part_host::ScratchCarve b(scratch, h.rec_bytes, h.cnt_bytes);
+  v4i32* recs = (v4i32*)b.recs;
+  const IdxSpill sl{b.spill_count(), (v4i32*)b.spill_entries(), d_err, h.g.spill_cap};
+  part_host::TimedLaunches timed{st, s};
+  for (part_host::Chunk c = part_host::next_chunk(fv, 0, h.chunk_rows); c.nf > 0;
+       c = part_host::next_chunk(fv, c.f0 + c.nf, h.chunk_rows)) {
+    hipError_t e = hipMemsetAsync(b.spill_base, 0, 256, s);
     if (e != hipSuccess) return e;
-    if (ev_pool && ev_i + 1 < st->n_ev) (void)hipEventRecord(ev_pool[ev_i], s);
-    e = idx_launch_scatter<NK, NV, RS, PK>(h, fv, f, f1 - f, recs, cnt, sl, s);
+    e = timed.run([&] { return idx_launch_scatter<NK, NV, RS, PK>(h, fv, c.f0, c.nf, recs, b.cnt, sl, s); });
     if (e != hipSuccess) return e;
-    if (ev_pool && ev_i + 1 < st->n_ev) {
-      (void)hipEventRecord(ev_pool[ev_i + 1], s);
-      ev_i += 2;
-    }
-    st->n_launches += 1;
     if constexpr (PK) {
-      e = idx_aggregate_pk<NV>(h, p, recs, cnt, out, n_cus, s);
+      e = idx_aggregate_pk<NV>(h, p, recs, b.cnt, out, n_cus, s);
     } else {
-      e = (NV > 0 && h.g.mm) ? idx_launch_aggregate<NK, NV, (NV > 0), RS>(h, p, recs, cnt, out, n_cus, s)
-                             : idx_launch_aggregate<NK, NV, false, RS>(h, p, recs, cnt, out, n_cus, s);
+      e = (NV > 0 && h.g.mm) ? idx_launch_aggregate<NK, NV, (NV > 0), RS>(h, p, recs, b.cnt, out, n_cus, s)
+                             : idx_launch_aggregate<NK, NV, false, RS>(h, p, recs, b.cnt, out, n_cus, s);
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_idx_spill<NK>, dim3(256), dim3(256), 0, s, h.g, h.c, p, sl, out);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    f = f1;
   }
-  st->spill_counter32 = (uint32_t*)spill_base;
-  st->n_events_used = ev_i;
+  st->spill_counter32 = b.spill_count();
+  st->n_events_used = timed.ev_i;
   return hipSuccess;
 }
 

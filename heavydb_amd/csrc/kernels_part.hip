@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "fast_common.h"
+#include "part_host.h"
 
 namespace mq {
 
@@ -246,36 +247,6 @@ struct Tile {
   Quad<VT> v;
   int valid;  // rows of this lane's quad that exist (0..4)
 };
-
-template <typename FT, typename VT>
-MQ_D void load_tile(const int8_t* const* __restrict__ cols, const int64_t* __restrict__ num_rows,
-                    int n_cols, int fcol, int kcol, int vcol, int f, int64_t tile_in_frag,
-                    Tile<FT, VT>& t) {
-  const int8_t* const* fc = cols + (size_t)f * n_cols;
-  const int64_t n = num_rows[f];
-  const int64_t q = tile_in_frag * kPartBlock + threadIdx.x;
-  const int64_t r0 = q << 2;
-  t.valid = 0;
-  if (r0 >= n) return;
-  const int8_t* fb = is_none<FT>::value ? nullptr : fc[fcol];
-  const int8_t* kb = fc[kcol];
-  const int8_t* vb = is_none<VT>::value ? nullptr : fc[vcol];
-  if (r0 + 4 <= n) {
-    load_quad<FT>(fb, q, t.f);
-    load_quad<int64_t>(kb, q, t.k);
-    load_quad<VT>(vb, q, t.v);
-    t.valid = 4;
-  } else {
-    t.valid = (int)(n - r0);
-    for (int i = 0; i < 4; ++i) {
-      if (i < t.valid) {
-        quad_set(t.f, i, load_one<FT>(fb, r0 + i));
-        t.k.v[i] = load_one<int64_t>(kb, r0 + i);
-        quad_set(t.v, i, load_one<VT>(vb, r0 + i));
-      }
-    }
-  }
-}
 
 // range filter on the column's own width (an int32 column is compared with 32-bit bounds;
 // make_range_filter clamps lo/hi to the column type)
@@ -2108,22 +2079,52 @@ __global__ __launch_bounds__(256) void k_join_payload(const int32_t* __restrict_
   if (__any(any_null) && (threadIdx.x & 63) == 0) atomicOr(flags, 1);
 }
 
-struct PartPlanHost {
+using part_host::Chunk;
+using part_host::RunFamily;
+using part_host::RunSizes;
+using part_host::ScratchCarve;
+using part_host::TimedLaunches;
+
+// the hash families' records are one 16-byte unit each; `ns_int` partial slots per spill entry
+RunFamily hash_runs(int ns_int) {
+  RunFamily f{};
+  f.recs_per_unit = 1;
+  f.unit_bytes = (int64_t)sizeof(Rec);
+  f.shrink = 0.97;
+  f.index_limit = (uint64_t)1 << 32;
+  f.spill_min = kSpillMin;
+  f.spill_max = 0x7fffffffll;
+  f.spill_entry_bytes = 8 * (int64_t)(1 + ns_int);
+  f.even_chunks = true;
+  return f;
+}
+
+// phase-1 LDS: staging lines + cursor / written / flushed + done + heavy-hitter table, then as many heavy-hitter
+// candidate slots as fit next to them (a power of two, 64 - 2048); 0 = not even 64 do
+size_t scatter_lds(uint32_t P, int ns_int, int32_t* n_cand) {
+  const size_t fixed = kStageRecs * sizeof(Rec) + (size_t)P * 12 + 48 + (size_t)kHotSlots * (8 + 8 * (size_t)ns_int);
+  *n_cand = 2048;
+  while (*n_cand > 64 && fixed + (size_t)*n_cand * 4 > 160 * 1024) *n_cand >>= 1;
+  const size_t lds = fixed + (size_t)*n_cand * 4;
+  return lds <= 160 * 1024 ? lds : 0;
+}
+
+SpillList spill_list(const ScratchCarve& c, int32_t* d_err, uint32_t cap, int ns_int) {
+  return SpillList{c.spill_count(), (int64_t*)c.spill_entries(), d_err, cap, 1 + ns_int};
+}
+
+// RunSizes: chunk_rows, the runs (rec_bytes), the run lengths + pair counters (cnt_bytes), spill_cap, scratch_bytes and,
+// overlapped, one of the two buffer sets (buf_bytes)
+struct PartPlanHost : RunSizes {
   PartGeom g;
   PartSlots ps;
-  int64_t chunk_rows;     // max rows per chunk
-  int64_t rec_bytes;      // runs
-  int64_t cnt_bytes;      // run lengths
-  int64_t scratch_bytes;  // runs + lengths + spill list
   size_t lds1, lds2;
-  uint32_t spill_cap;     // spill list entries
-  int n_cand;             // heavy-hitter candidate slots in phase 1
+  int32_t n_cand;         // heavy-hitter candidate slots in phase 1
   int op_mask;            // set of internal ops (bit per SlotOp)
   // phase 1 of chunk i + 1 next to phase 2 of chunk i: two buffers of `buf_bytes` (runs + lengths +
   // spill list) in the scratch, g.B scatter workgroups and grid2 aggregate workgroups share the device
   int overlap;            // 0 = one phase after the other on the whole device
   int grid2;              // workgroups of phase 2
-  int64_t buf_bytes;      // one buffer set (256-byte multiple)
 };
 
 constexpr size_t kLdsTableBudget = 150 * 1024;
@@ -2216,10 +2217,7 @@ bool make_part_plan(const DevPlan& p, const FastShape& fs, const FragView& fv, i
   while (P < 1024 && P < (uint32_t)n_cus && (uint64_t)P * 4 <= d) P <<= 1;
   const uint32_t R = (uint32_t)((units + P - 1) / P);
   if (R > (uint32_t)kMaxSub) return false;
-  h.g.P = (int32_t)P;
-  h.g.L = kStageRecs / P;
-  h.g.lgL = 0;
-  while ((1u << h.g.lgL) < h.g.L) ++h.g.lgL;
+  part_host::line_geometry(h.g, kStageRecs, P);
   HomeMap& hm = h.g.hm;
   hm.d = (uint32_t)d;
   hm.S1 = (uint32_t)((d + P - 1) / P);
@@ -2259,62 +2257,16 @@ bool make_part_plan(const DevPlan& p, const FastShape& fs, const FragView& fv, i
       h.overlap = 1;
       h.g.B = ov;
       h.grid2 = n_cus - ov;
-      scratch_cap /= 2;
     }
   }
-  // chunking: worst case every row survives the filter; shrink the chunk until the runs
-  // (1.2 x mean + 6 sigma + a line of slack per run) fit the scratch cap, never below one
-  // fragment
-  int64_t chunk_rows = fv.total_rows > 0 ? fv.total_rows : 1;
-  if (h.overlap) {
-    const int64_t want = (fv.total_rows + kOverlapMinChunks - 1) / kOverlapMinChunks + fv.max_frag_rows;
-    if (want < chunk_rows) chunk_rows = want;
-    if (chunk_rows < fv.max_frag_rows) chunk_rows = fv.max_frag_rows;
-  }
-  if (chunk_rows > 0xfff00000ll) chunk_rows = 0xfff00000ll;  // 32-bit LDS counters per chunk
-  for (;;) {
-    const double per_run = (double)chunk_rows / ((double)P * h.g.B);
-    uint64_t cap = (uint64_t)(per_run * 1.2 + 6.0 * __builtin_sqrt(per_run + 1.0)) + h.g.L;
-    cap = (cap + h.g.L - 1) / h.g.L * h.g.L;  // whole lines
-    if (cap > 0x7fffffffull) return false;
-    if ((uint64_t)P * h.g.B * cap >= ((uint64_t)1 << 32)) {  // 32-bit record indices in phase 1
-      if (chunk_rows <= fv.max_frag_rows) return false;
-      chunk_rows = (int64_t)(chunk_rows * 0.97);
-      if (chunk_rows < fv.max_frag_rows) chunk_rows = fv.max_frag_rows;
-      continue;
-    }
-    h.g.cap = (uint32_t)cap;
-    h.rec_bytes = (int64_t)P * h.g.B * (int64_t)cap * (int64_t)sizeof(Rec);
-    h.cnt_bytes = (((int64_t)P * h.g.B * 4 + 255) & ~255ll) + kPairCtrBytes;  // run lengths + the pair counters of phase 2
-    // spill list: room for 1/16 of the chunk's rows (skewed keys overflow their runs by a few
-    // per cent of the records), at least kSpillMin entries
-    int64_t spill_cap = chunk_rows / 16;
-    if (spill_cap < (int64_t)kSpillMin) spill_cap = kSpillMin;
-    if (spill_cap > 0x7fffffffll) spill_cap = 0x7fffffffll;
-    h.spill_cap = (uint32_t)spill_cap;
-    const int64_t spill_bytes = 256 + spill_cap * 8 * (int64_t)(1 + n_int);
-    h.buf_bytes = (h.rec_bytes + h.cnt_bytes + spill_bytes + 255) & ~255ll;
-    h.scratch_bytes = h.overlap ? 2 * h.buf_bytes : h.rec_bytes + h.cnt_bytes + spill_bytes;
-    if (h.buf_bytes <= scratch_cap || chunk_rows <= fv.max_frag_rows) break;
-    chunk_rows = (int64_t)(chunk_rows * 0.97);
-    if (chunk_rows < fv.max_frag_rows) chunk_rows = fv.max_frag_rows;
-  }
-  // equal-sized chunks: 10 B rows under a 3.4 B-row limit are three chunks of 3.3 B, not two full
-  // ones and a sliver (every chunk pays the table re-load, the emission and the launch tails)
-  if (fv.total_rows > chunk_rows) {
-    const int64_t n_chunks = (fv.total_rows + chunk_rows - 1) / chunk_rows;
-    const int64_t even = (fv.total_rows + n_chunks - 1) / n_chunks + fv.max_frag_rows;  // fragments are not split
-    if (even < chunk_rows) chunk_rows = even;
-  }
-  h.chunk_rows = chunk_rows;
-  // staging lines + cursor / written / flushed + done + heavy-hitter table
-  {
-    const size_t fixed = kStageRecs * sizeof(Rec) + (size_t)P * 12 + 48 + (size_t)kHotSlots * (8 + 8 * (size_t)n_int);
-    h.n_cand = 2048;
-    while (h.n_cand > 64 && fixed + (size_t)h.n_cand * 4 > 160 * 1024) h.n_cand >>= 1;
-    h.lds1 = fixed + (size_t)h.n_cand * 4;
-    if (h.lds1 > 160 * 1024) return false;
-  }
+  RunFamily rf = hash_runs(n_int);
+  rf.big_cap_refuses = true;
+  rf.cnt_extra_bytes = kPairCtrBytes;  // the pair counters of phase 2
+  rf.fit_rounded = true;
+  rf.overlap_min_chunks = h.overlap ? kOverlapMinChunks : 0;
+  if (!part_host::size_runs(fv.total_rows, fv.max_frag_rows, P, h.g.B, h.g.L, scratch_cap, rf, &h)) return false;
+  h.g.cap = h.cap;
+  if (!(h.lds1 = scatter_lds(P, n_int, &h.n_cand))) return false;
   h.lds2 = (size_t)h.g.E * entry_bytes + (size_t)((hm.S2 + 31) / 32) * 4 + (size_t)h.g.B * 4;
   return h.lds2 <= 160 * 1024;
 }
@@ -2342,32 +2294,104 @@ OverlapRes* overlap_resources() {
   return &r;
 }
 
-template <typename FT, typename VT>
-hipError_t launch_scatter_t(int grid, size_t lds, hipStream_t s, const FragView& fv, int f0, int nf,
+// phase-2 member: the common op sets are compiled in, everything else runs the generic one
+using AggKernel = decltype(&k_part_aggregate<0>);
+AggKernel aggregate_member(int op_mask, size_t lds2) {
+  AggKernel k = k_part_aggregate<0>;
+  switch (op_mask) {
+    case 1 << SO_COUNT: k = k_part_aggregate<(1 << SO_COUNT)>; break;
+    case (1 << SO_COUNT) | (1 << SO_SUM_F): k = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_F))>; break;
+    case (1 << SO_COUNT) | (1 << SO_SUM_I): k = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_I))>; break;
+    case 1 << SO_SUM_F: k = k_part_aggregate<(1 << SO_SUM_F)>; break;
+    case 1 << SO_SUM_I: k = k_part_aggregate<(1 << SO_SUM_I)>; break;
+    // nullable value column: COUNT(*), AVG(col) [, COUNT(col)]
+    case (1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN):
+      k = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN))>;
+      break;
+    case (1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN):
+      k = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN))>;
+      break;
+    default: break;
+  }
+  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+  return k;
+}
+
+// Phase 2 on stream `s`: k_part_aggregate over the records of one chunk (chunk > 0 re-loads the table rows the earlier
+// chunks wrote) or, with no records, over the slices of `ms`; then k_spill_merge over what either phase spilled.  `rows`
+// is the chunk's row count, held to what a 32-bit LDS counter takes (a slice merge passes its own bound, which is below
+// that for any n_src).  The pair counters, where used, are zeroed first.
+hipError_t launch_aggregate(AggKernel k, const PartPlanHost& h, const TableArgs& tab, hipStream_t s, const Rec* recs,
+                            const uint32_t* cnt, const SpillList& sl, int chunk, int64_t rows, unsigned long long* dbg,
+                            unsigned int* pair_ctr, const SliceMerge& ms) {
+  hipError_t e;
+  if (pair_ctr && (e = hipMemsetAsync(pair_ctr, 0, kPairCtrBytes, s)) != hipSuccess) return e;
+  const int units = h.g.P * (int)h.g.hm.R;
+  hipLaunchKernelGGL(k, dim3(units < h.grid2 ? units : h.grid2), dim3(kPartBlock), h.lds2, s, h.g, recs, cnt, h.ps, tab, sl,
+                     chunk > 0 ? 1 : 0, (uint32_t)(rows > 0xfff00000ll ? 0xfff00000ll : rows), dbg, pair_ctr, ms);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  (void)hipFuncSetAttribute((const void*)k_spill_merge, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            h.g.ns_int * kSpillLds * 8);
+  hipLaunchKernelGGL(k_spill_merge, dim3(512), dim3(256), (size_t)h.g.ns_int * kSpillLds * 8, s, h.ps, tab, sl,
+                     h.g.ns_int);
+  return hipGetLastError();
+}
+
+// one member of k_part_scatter over the fragments of chunk `c`, into buffer set `b`
+template <typename FT, typename VT, int MODE>
+hipError_t launch_scatter_t(int grid, size_t lds, hipStream_t s, const FragView& fv, const Chunk& c,
                             const RangeFilter& flt, int kcol, int vcol, const ScatterArgs& g,
-                            Rec* scratch, uint32_t* cnt, const SpillList& sl) {
-  const int8_t* const* cols = fv.d_cols + (size_t)f0 * fv.n_cols;
-  const int64_t* rows = fv.d_num_rows + f0;
+                            const ScratchCarve& b, const SpillList& sl) {
+  const int8_t* const* cols = fv.d_cols + (size_t)c.f0 * fv.n_cols;
+  const int64_t* rows = fv.d_num_rows + c.f0;
   // opt in to > 64 KB of dynamic LDS (gfx950: 160 KB per workgroup)
-  (void)hipFuncSetAttribute((const void*)k_part_scatter<FT, VT>,
+  (void)hipFuncSetAttribute((const void*)k_part_scatter<FT, VT, MODE>,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_part_scatter<FT, VT>), dim3(grid), dim3(kPartBlock), lds, s, cols, rows, nf,
-                     fv.n_cols, flt, kcol, vcol, g, scratch, cnt, sl);
+  hipLaunchKernelGGL((k_part_scatter<FT, VT, MODE>), dim3(grid), dim3(kPartBlock), lds, s, cols, rows, c.nf,
+                     fv.n_cols, flt, kcol, vcol, g, (Rec*)b.recs, b.cnt, sl);
   return hipGetLastError();
 }
 
 template <typename FT>
 hipError_t launch_scatter_v(const FastShape& fs, int grid, size_t lds, hipStream_t s,
-                            const FragView& fv, int f0, int nf, int kcol, const ScatterArgs& g,
-                            Rec* scratch, uint32_t* cnt, const SpillList& sl) {
+                            const FragView& fv, const Chunk& c, int kcol, const ScatterArgs& g,
+                            const ScratchCarve& b, const SpillList& sl) {
   const int vcol = fs.vcol < 0 ? 0 : fs.vcol;
   if (fs.vcol < 0)
-    return launch_scatter_t<FT, none_t>(grid, lds, s, fv, f0, nf, fs.flt, kcol, vcol, g, scratch, cnt, sl);
+    return launch_scatter_t<FT, none_t, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
   if (fs.vtype == MI355Q_INT64)
-    return launch_scatter_t<FT, int64_t>(grid, lds, s, fv, f0, nf, fs.flt, kcol, vcol, g, scratch, cnt, sl);
+    return launch_scatter_t<FT, int64_t, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
   if (fs.vtype == MI355Q_INT32)
-    return launch_scatter_t<FT, int32_t>(grid, lds, s, fv, f0, nf, fs.flt, kcol, vcol, g, scratch, cnt, sl);
-  return launch_scatter_t<FT, double>(grid, lds, s, fv, f0, nf, fs.flt, kcol, vcol, g, scratch, cnt, sl);
+    return launch_scatter_t<FT, int32_t, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
+  return launch_scatter_t<FT, double, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
+}
+
+// GROUP BY: the member for the filter column's type and the value column's
+hipError_t launch_scatter(const FastShape& fs, int grid, size_t lds, hipStream_t s, const FragView& fv, const Chunk& c,
+                          int kcol, const ScatterArgs& g, const ScratchCarve& b, const SpillList& sl) {
+  if (fs.fil_type == 0) return launch_scatter_v<none_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+  if (fs.fil_type == MI355Q_INT32) return launch_scatter_v<int32_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+  if (fs.fil_type == MI355Q_INT8) return launch_scatter_v<int8_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+  return launch_scatter_v<int64_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+}
+
+// join probes (MODE 1 DIRECT, 2 keyed): no filter, an int64 value column (`vcol` >= 0) or none
+template <int MODE>
+hipError_t launch_scatter_direct(int vcol, size_t lds, hipStream_t s, const FragView& fv, const Chunk& c, int kcol,
+                                 const ScatterArgs& g, const ScratchCarve& b, const SpillList& sl) {
+  const RangeFilter flt = no_filter();
+  if (vcol >= 0) return launch_scatter_t<none_t, int64_t, MODE>(g.B, lds, s, fv, c, flt, kcol, vcol, g, b, sl);
+  return launch_scatter_t<none_t, none_t, MODE>(g.B, lds, s, fv, c, flt, kcol, 0, g, b, sl);
+}
+
+TableArgs make_table_args(const DevPlan& p, const FastShape& fs, int64_t* out) {
+  TableArgs tab{};
+  tab.out = out;
+  tab.entry_count = (uint32_t)p.entry_count;
+  tab.row_quad = p.row_quad;
+  tab.sp = fs.sp;
+  for (int j = 0; j < MI355Q_MAX_SLOTS; ++j) tab.init[j] = p.init_vals[j];
+  return tab;
 }
 
 }  // namespace
@@ -2382,7 +2406,6 @@ bool part_supported(const DevPlan& p, const FragView& fv, int n_cus) {
 int64_t part_scratch_bytes(const DevPlan& p, const FragView& fv, int n_cus, int64_t cap_bytes) {
   FastShape fs;
   if (!grouped_fast_shape(p, fv, &fs)) return 0;
-  if (cap_bytes <= 0) cap_bytes = kDefaultScratchCap;
   PartPlanHost h;
   if (!make_part_plan(p, fs, fv, n_cus, cap_bytes, &h)) return 0;
   return h.scratch_bytes + 64;
@@ -2394,52 +2417,24 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
                                        LaunchStats* st) {
   FastShape fs;
   if (!grouped_fast_shape(p, fv, &fs)) return hipErrorInvalidValue;
-  if (cap_bytes <= 0) cap_bytes = kDefaultScratchCap;
   PartPlanHost h;
   // same inputs as part_scratch_bytes -> the same plan
   if (!make_part_plan(p, fs, fv, n_cus, cap_bytes, &h)) return hipErrorInvalidValue;
   if (h.scratch_bytes + 64 > scratch_bytes) return hipErrorInvalidValue;
-  hipEvent_t* ev_pool = st->ev_pool;
-  const int n_ev = st->n_ev;
-  Rec* recs = (Rec*)scratch;
-  uint32_t* cnt = (uint32_t*)((char*)scratch + h.rec_bytes);
-  char* spill_base = (char*)scratch + h.rec_bytes + h.cnt_bytes;
-  SpillList sl{(uint32_t*)spill_base, (int64_t*)(spill_base + 256), d_err, h.spill_cap, 1 + h.g.ns_int};
-  hipError_t e = hipMemsetAsync(spill_base, 0, 256, s);
+  // buffer set b of the scratch (one, or the two of the overlapped pipeline), its spill list and its pair counters
+  auto buffers = [&](int b) { return ScratchCarve(scratch, h.rec_bytes, h.cnt_bytes, b, h.buf_bytes); };
+  auto spills = [&](const ScratchCarve& b) { return spill_list(b, d_err, h.spill_cap, h.g.ns_int); };
+  const uint32_t opt_flags = tune_knobs().flags;
+  const bool pairs = h.grid2 <= 256 && !(opt_flags & MI355Q_OPT_NO_PAIR_RENDEZVOUS);
+  auto pair_ctr = [&](const ScratchCarve& b) { return pairs ? (unsigned int*)(b.spill_base - kPairCtrBytes) : nullptr; };
+  const ScratchCarve b0 = buffers(0);
+  hipError_t e = hipMemsetAsync(b0.spill_base, 0, 256, s);
   if (e != hipSuccess) return e;
-  TableArgs tab{};
-  tab.out = out;
-  tab.entry_count = (uint32_t)p.entry_count;
-  tab.row_quad = p.row_quad;
-  tab.sp = fs.sp;
-  for (int j = 0; j < MI355Q_MAX_SLOTS; ++j) tab.init[j] = p.init_vals[j];
+  const TableArgs tab = make_table_args(p, fs, out);
   st->kernel_name = "k_part_scatter";
   st->variant = 2;
   st->n_launches = 0;
-  // phase-2 member: the common op sets are compiled in, everything else runs the generic one
-  auto agg_kernel = k_part_aggregate<0>;
-  switch (h.op_mask) {
-    case 1 << SO_COUNT: agg_kernel = k_part_aggregate<(1 << SO_COUNT)>; break;
-    case (1 << SO_COUNT) | (1 << SO_SUM_F): agg_kernel = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_F))>; break;
-    case (1 << SO_COUNT) | (1 << SO_SUM_I): agg_kernel = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_I))>; break;
-    case 1 << SO_SUM_F: agg_kernel = k_part_aggregate<(1 << SO_SUM_F)>; break;
-    case 1 << SO_SUM_I: agg_kernel = k_part_aggregate<(1 << SO_SUM_I)>; break;
-    // nullable value column: COUNT(*), AVG(col) [, COUNT(col)]
-    case (1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN):
-      agg_kernel = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN))>;
-      break;
-    case (1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN):
-      agg_kernel = k_part_aggregate<((1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN))>;
-      break;
-    default: break;
-  }
-  (void)hipFuncSetAttribute((const void*)agg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)h.lds2);
-  // MI355Q_OPT_TRACE: per-phase cycle counters of phase 2 live in the spill header's tail
-  const uint32_t opt_flags = tune_knobs().flags;
-  unsigned long long* dbg = (opt_flags & MI355Q_OPT_TRACE) ? (unsigned long long*)(spill_base + 64) : nullptr;
-  unsigned int* pair_ctr = (n_cus <= 256 && !(opt_flags & MI355Q_OPT_NO_PAIR_RENDEZVOUS))
-                               ? (unsigned int*)((char*)scratch + h.rec_bytes + h.cnt_bytes - kPairCtrBytes) : nullptr;
+  const AggKernel agg_kernel = aggregate_member(h.op_mask, h.lds2);
   ScatterArgs sa{};
   sa.P = h.g.P;
   sa.lgL = h.g.lgL;
@@ -2453,9 +2448,10 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
   for (int m = 0; m < h.g.ns_int; ++m) sa.ops_packed |= (uint32_t)(h.ps.int_op[m] & 15) << (4 * m);
   sa.val_nullable = h.ps.val_nullable;
   sa.null_bits = h.ps.null_bits;
-  int f = 0;
-  int ev_i = 0;
-  int chunk = 0;
+  TimedLaunches timed{st, s};
+  auto scatter_chunk = [&](const Chunk& c, const ScratchCarve& b) {
+    return timed.run([&] { return launch_scatter(fs, h.g.B, h.lds1, s, fv, c, p.group_col, sa, b, spills(b)); });
+  };
   if (h.overlap) {
     // ---- phase 1 of chunk i + 1 on g.B CUs next to phase 2 of chunk i on the other grid2 ----
     // stream s: scatter(0), scatter(1), ...  (scatter(i) waits until aggregate(i - 2) has let go of its buffer)
@@ -2465,69 +2461,26 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
     // enqueued): scatter(0); then scatter(i + 1), aggregate(i) for every i.
     OverlapRes* ov = overlap_resources();
     if (!ov) return hipErrorInvalidValue;
-    struct Chunk { int f0, nf; int64_t rows; };
     std::vector<Chunk> chunks;
-    while (f < fv.n_frags) {
-      int64_t rows = 0;
-      int f1 = f;
-      while (f1 < fv.n_frags && (f1 == f || rows + fv.h_num_rows[f1] <= h.chunk_rows)) {
-        rows += fv.h_num_rows[f1];
-        ++f1;
-      }
-      chunks.push_back({f, f1 - f, rows});
-      f = f1;
-    }
+    for (Chunk c = part_host::next_chunk(fv, 0, h.chunk_rows); c.nf > 0; c = part_host::next_chunk(fv, c.f0 + c.nf, h.chunk_rows))
+      chunks.push_back(c);
     const int n = (int)chunks.size();
-    auto buf_recs = [&](int b) { return (Rec*)((char*)scratch + (int64_t)b * h.buf_bytes); };
-    auto buf_cnt = [&](int b) { return (uint32_t*)((char*)scratch + (int64_t)b * h.buf_bytes + h.rec_bytes); };
-    auto buf_spill = [&](int b) { return (char*)scratch + (int64_t)b * h.buf_bytes + h.rec_bytes + h.cnt_bytes; };
-    auto buf_sl = [&](int b) {
-      char* sb = buf_spill(b);
-      return SpillList{(uint32_t*)sb, (int64_t*)(sb + 256), d_err, h.spill_cap, 1 + h.g.ns_int};
-    };
     auto scatter = [&](int i) -> hipError_t {
-      const int b = i & 1;
+      const ScratchCarve b = buffers(i & 1);
       hipError_t e2;
-      if (i >= 2 && (e2 = hipStreamWaitEvent(s, ov->ev_agg[b], 0)) != hipSuccess) return e2;
-      if ((e2 = hipMemsetAsync(buf_spill(b), 0, 256, s)) != hipSuccess) return e2;
-      if (ev_pool && ev_i + 1 < n_ev) (void)hipEventRecord(ev_pool[ev_i], s);
-      const Chunk& c = chunks[i];
-      if (fs.fil_type == 0)
-        e2 = launch_scatter_v<none_t>(fs, h.g.B, h.lds1, s, fv, c.f0, c.nf, p.group_col, sa, buf_recs(b), buf_cnt(b), buf_sl(b));
-      else if (fs.fil_type == MI355Q_INT32)
-        e2 = launch_scatter_v<int32_t>(fs, h.g.B, h.lds1, s, fv, c.f0, c.nf, p.group_col, sa, buf_recs(b), buf_cnt(b), buf_sl(b));
-      else if (fs.fil_type == MI355Q_INT8)
-        e2 = launch_scatter_v<int8_t>(fs, h.g.B, h.lds1, s, fv, c.f0, c.nf, p.group_col, sa, buf_recs(b), buf_cnt(b), buf_sl(b));
-      else
-        e2 = launch_scatter_v<int64_t>(fs, h.g.B, h.lds1, s, fv, c.f0, c.nf, p.group_col, sa, buf_recs(b), buf_cnt(b), buf_sl(b));
-      if (e2 != hipSuccess) return e2;
-      if (ev_pool && ev_i + 1 < n_ev) {
-        (void)hipEventRecord(ev_pool[ev_i + 1], s);
-        ev_i += 2;
-      }
-      st->n_launches += 1;
-      return hipEventRecord(ov->ev_scat[b], s);
+      if (i >= 2 && (e2 = hipStreamWaitEvent(s, ov->ev_agg[i & 1], 0)) != hipSuccess) return e2;
+      if ((e2 = hipMemsetAsync(b.spill_base, 0, 256, s)) != hipSuccess) return e2;
+      if ((e2 = scatter_chunk(chunks[i], b)) != hipSuccess) return e2;
+      return hipEventRecord(ov->ev_scat[i & 1], s);
     };
     auto aggregate = [&](int i) -> hipError_t {
-      const int b = i & 1;
-      const Chunk& c = chunks[i];
+      const ScratchCarve b = buffers(i & 1);
       hipError_t e2;
-      if ((e2 = hipStreamWaitEvent(ov->s2, ov->ev_scat[b], 0)) != hipSuccess) return e2;
-      unsigned int* pc = (h.grid2 <= 256 && !(opt_flags & MI355Q_OPT_NO_PAIR_RENDEZVOUS))
-                             ? (unsigned int*)((char*)buf_cnt(b) + h.cnt_bytes - kPairCtrBytes) : nullptr;
-      if (pc && (e2 = hipMemsetAsync(pc, 0, kPairCtrBytes, ov->s2)) != hipSuccess) return e2;
-      const int units = h.g.P * (int)h.g.hm.R;
-      const int g2 = units < h.grid2 ? units : h.grid2;
-      hipLaunchKernelGGL(agg_kernel, dim3(g2), dim3(kPartBlock), h.lds2, ov->s2, h.g, buf_recs(b), buf_cnt(b), h.ps,
-                         tab, buf_sl(b), i > 0 ? 1 : 0, (uint32_t)(c.rows > 0xfff00000ll ? 0xfff00000ll : c.rows),
-                         (unsigned long long*)nullptr, pc, SliceMerge{});
-      if ((e2 = hipGetLastError()) != hipSuccess) return e2;
-      (void)hipFuncSetAttribute((const void*)k_spill_merge, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                h.g.ns_int * kSpillLds * 8);
-      hipLaunchKernelGGL(k_spill_merge, dim3(512), dim3(256), (size_t)h.g.ns_int * kSpillLds * 8, ov->s2, h.ps, tab,
-                         buf_sl(b), h.g.ns_int);
-      if ((e2 = hipGetLastError()) != hipSuccess) return e2;
-      return hipEventRecord(ov->ev_agg[b], ov->s2);
+      if ((e2 = hipStreamWaitEvent(ov->s2, ov->ev_scat[i & 1], 0)) != hipSuccess) return e2;
+      if ((e2 = launch_aggregate(agg_kernel, h, tab, ov->s2, (const Rec*)b.recs, b.cnt, spills(b), i, chunks[i].rows, nullptr,
+                                 pair_ctr(b), SliceMerge{})) != hipSuccess)
+        return e2;
+      return hipEventRecord(ov->ev_agg[i & 1], ov->s2);
     };
     // everything enqueued on s so far (table init by the caller, the memsets above) precedes the first aggregate
     // through ev_scat[0]
@@ -2537,63 +2490,31 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
       if ((e = aggregate(i)) != hipSuccess) return e;
     }
     if ((e = hipStreamWaitEvent(s, ov->ev_agg[(n - 1) & 1], 0)) != hipSuccess) return e;
-    st->spill_counter32 = (uint32_t*)buf_spill((n - 1) & 1);
-    st->n_events_used = ev_i;
+    st->spill_counter32 = buffers((n - 1) & 1).spill_count();
+    st->n_events_used = timed.ev_i;
     return hipSuccess;
   }
-  while (f < fv.n_frags) {
-    int64_t rows = 0;
-    int f1 = f;
-    while (f1 < fv.n_frags && (f1 == f || rows + fv.h_num_rows[f1] <= h.chunk_rows)) {
-      rows += fv.h_num_rows[f1];
-      ++f1;
-    }
-    if (ev_pool && ev_i + 1 < n_ev) (void)hipEventRecord(ev_pool[ev_i], s);
-    if (fs.fil_type == 0)
-      e = launch_scatter_v<none_t>(fs, h.g.B, h.lds1, s, fv, f, f1 - f, p.group_col, sa, recs, cnt, sl);
-    else if (fs.fil_type == MI355Q_INT32)
-      e = launch_scatter_v<int32_t>(fs, h.g.B, h.lds1, s, fv, f, f1 - f, p.group_col, sa, recs, cnt, sl);
-    else if (fs.fil_type == MI355Q_INT8)
-      e = launch_scatter_v<int8_t>(fs, h.g.B, h.lds1, s, fv, f, f1 - f, p.group_col, sa, recs, cnt, sl);
-    else
-      e = launch_scatter_v<int64_t>(fs, h.g.B, h.lds1, s, fv, f, f1 - f, p.group_col, sa, recs, cnt, sl);
-    if (e != hipSuccess) return e;
-    if (ev_pool && ev_i + 1 < n_ev) {
-      (void)hipEventRecord(ev_pool[ev_i + 1], s);
-      ev_i += 2;
-    }
-    st->n_launches += 1;
-    const int units = h.g.P * (int)h.g.hm.R;
-    const int grid2 = units < h.grid2 ? units : h.grid2;
-    if (pair_ctr) {
-      e = hipMemsetAsync(pair_ctr, 0, kPairCtrBytes, s);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(agg_kernel, dim3(grid2), dim3(kPartBlock), h.lds2, s, h.g, recs, cnt, h.ps,
-                       tab, sl, chunk > 0 ? 1 : 0, (uint32_t)(rows > 0xfff00000ll ? 0xfff00000ll : rows), dbg,
-                       pair_ctr, SliceMerge{});
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    (void)hipFuncSetAttribute((const void*)k_spill_merge, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              h.g.ns_int * kSpillLds * 8);
-    hipLaunchKernelGGL(k_spill_merge, dim3(512), dim3(256), (size_t)h.g.ns_int * kSpillLds * 8, s, h.ps, tab, sl,
-                       h.g.ns_int);
-    e = hipGetLastError();
+  // MI355Q_OPT_TRACE: per-phase cycle counters of phase 2 live in the spill header's tail
+  unsigned long long* dbg = (opt_flags & MI355Q_OPT_TRACE) ? (unsigned long long*)(b0.spill_base + 64) : nullptr;
+  int chunk = 0;
+  for (Chunk c = part_host::next_chunk(fv, 0, h.chunk_rows); c.nf > 0; c = part_host::next_chunk(fv, c.f0 + c.nf, h.chunk_rows)) {
+    if ((e = scatter_chunk(c, b0)) != hipSuccess) return e;
+    e = launch_aggregate(agg_kernel, h, tab, s, (const Rec*)b0.recs, b0.cnt, spills(b0), chunk, c.rows, dbg, pair_ctr(b0),
+                         SliceMerge{});
     if (e != hipSuccess) return e;
     // spilled_rows reports the last chunk's list; the word is re-armed for the next chunk
-    if (f1 < fv.n_frags) {
-      e = hipMemsetAsync(spill_base, 0, 4, s);
+    if (c.f0 + c.nf < fv.n_frags) {
+      e = hipMemsetAsync(b0.spill_base, 0, 4, s);
       if (e != hipSuccess) return e;
     }
-    f = f1;
     ++chunk;
   }
-  st->spill_counter32 = (uint32_t*)spill_base;
-  st->n_events_used = ev_i;
+  st->spill_counter32 = b0.spill_count();
+  st->n_events_used = timed.ev_i;
   if (dbg) {
     unsigned long long h_dbg[16] = {0};
     uint32_t h_sp = 0;
-    (void)hipMemcpy(&h_sp, spill_base, 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(&h_sp, b0.spill_base, 4, hipMemcpyDeviceToHost);
     (void)hipStreamSynchronize(s);
     (void)hipMemcpy(h_dbg, dbg, sizeof(h_dbg), hipMemcpyDeviceToHost);
     const double wg = (double)(h.g.P * (int)h.g.hm.R < n_cus ? h.g.P * (int)h.g.hm.R : n_cus);
@@ -2660,16 +2581,10 @@ hipError_t launch_slice_merge(const DevPlan& p, int64_t* out, const int64_t* con
   if (!slice_merge_plan(p, n_cus, &fs, &h)) return hipErrorInvalidValue;
   const uint32_t spill_cap = slice_merge_spill_cap(lo, hi);
   if (256 + (int64_t)spill_cap * 8 * (1 + h.g.ns_int) > scratch_bytes) return hipErrorInvalidValue;
-  char* spill_base = (char*)scratch;
-  SpillList sl{(uint32_t*)spill_base, (int64_t*)(spill_base + 256), d_err, spill_cap, 1 + h.g.ns_int};
-  hipError_t e = hipMemsetAsync(spill_base, 0, 256, s);
+  const ScratchCarve b(scratch, 0, 0);  // no records: the spill list alone
+  hipError_t e = hipMemsetAsync(b.spill_base, 0, 256, s);
   if (e != hipSuccess) return e;
-  TableArgs tab{};
-  tab.out = out;
-  tab.entry_count = (uint32_t)p.entry_count;
-  tab.row_quad = p.row_quad;
-  tab.sp = fs.sp;
-  for (int j = 0; j < MI355Q_MAX_SLOTS; ++j) tab.init[j] = p.init_vals[j];
+  const TableArgs tab = make_table_args(p, fs, out);
   SliceMerge ms{};
   for (int i = 0; i < n_src; ++i) {
     ms.src[i] = src[i];
@@ -2679,36 +2594,49 @@ hipError_t launch_slice_merge(const DevPlan& p, int64_t* out, const int64_t* con
   ms.pad_rows = pads ? pad_rows : 0;
   ms.lo = (uint32_t)lo;
   ms.hi = (uint32_t)hi;
-  auto agg_kernel = k_part_aggregate<0>;  // no records in this mode: the op-set members gain nothing
-  (void)hipFuncSetAttribute((const void*)agg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds2);
-  const int units = h.g.P * (int)h.g.hm.R;
-  const int grid2 = units < n_cus ? units : n_cus;
   // 32-bit LDS counters: n_src partial counts are added up per group; a partial that could make the sum
   // wrap goes through the 64-bit spill merge instead
   const uint32_t big_from = 0xffffffffu - 0xffffffffu / (uint32_t)(n_src + 1);
-  hipLaunchKernelGGL(agg_kernel, dim3(grid2), dim3(kPartBlock), h.lds2, s, h.g, (const Rec*)nullptr,
-                     (const uint32_t*)nullptr, h.ps, tab, sl, 0, big_from, (unsigned long long*)nullptr,
-                     (unsigned int*)nullptr, ms);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  (void)hipFuncSetAttribute((const void*)k_spill_merge, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            h.g.ns_int * kSpillLds * 8);
-  hipLaunchKernelGGL(k_spill_merge, dim3(512), dim3(256), (size_t)h.g.ns_int * kSpillLds * 8, s, h.ps, tab, sl,
-                     h.g.ns_int);
-  return hipGetLastError();
+  // (no records in this mode: the op-set members gain nothing)
+  return launch_aggregate(aggregate_member(0, h.lds2), h, tab, s, nullptr, nullptr, spill_list(b, d_err, spill_cap, h.g.ns_int),
+                          0, big_from, nullptr, nullptr, ms);
 }
 
 // ---------------------------------------------------------------- radix join probe: host side
 namespace {
 
-struct JoinPartHost {
+struct JoinPartHost : RunSizes {
   ScatterArgs sa;
   JoinPartArgs ja;
-  int64_t chunk_rows, rec_bytes, cnt_bytes, scratch_bytes;
   size_t lds1, lds2;
-  uint32_t spill_cap;
   int vcol;  // fact value column or -1
 };
+
+// Phase 1 of the join probes: DIRECT partitioning (partition = (key - kmin) / S1 over `range` keys or table slots), its
+// runs and its LDS.  Spilled / heavy-hitter records leave as partial rows of SUM, COUNT, COUNT of non-NULL values.
+bool plan_direct_scatter(const FragView& fv, int n_cus, int64_t scratch_cap, uint32_t P, uint64_t range, uint32_t S1,
+                         int64_t kmin, bool even_chunks, ScatterArgs* out, RunSizes* runs, size_t* lds1) {
+  ScatterArgs& sa = *out;
+  sa = ScatterArgs{};
+  part_host::line_geometry(sa, kStageRecs, P);
+  sa.B = n_cus;
+  sa.hm.d = (uint32_t)range;
+  sa.hm.S1 = S1;
+  sa.hm.S2 = S1;
+  sa.hm.R = 1;
+  sa.hm.d_rcp = (uint32_t)(((uint64_t)1 << 32) / sa.hm.d);
+  sa.hm.s1_rcp = (uint32_t)(((uint64_t)1 << 32) / S1);
+  sa.kmin = kmin;
+  sa.ns_int = 3;
+  sa.ops_packed = (uint32_t)SO_SUM_I | ((uint32_t)SO_COUNT << 4) | ((uint32_t)SO_COUNT_NN << 8);
+  sa.val_nullable = 1;  // the non-grouped SUM skips NULL_BIGINT even on a NOT NULL column
+  sa.null_bits = INT64_MIN;
+  RunFamily rf = hash_runs(sa.ns_int);
+  rf.even_chunks = even_chunks;
+  if (!part_host::size_runs(fv.total_rows, fv.max_frag_rows, P, sa.B, sa.L, scratch_cap, rf, runs)) return false;
+  sa.cap = runs->cap;
+  return (*lds1 = scatter_lds(P, sa.ns_int, &sa.n_cand)) != 0;
+}
 
 // the plan shapes this family takes: non-grouped, INNER one-to-one perfect join on a NOT NULL
 // int64 key with the presence bitmap available, targets COUNT(*) / SUM(fact int64 NOT NULL col)
@@ -2747,57 +2675,9 @@ bool make_join_part_plan(const DevPlan& p, const FragView& fv, int n_cus, int64_
   while (P < 1024 && (P < 4 * (uint32_t)n_cus || s1_of(P) / 8 > 120 * 1024) && s1_of(P * 2) >= 64) P <<= 1;
   const uint32_t S1 = s1_of(P);
   if (S1 / 8 > 150 * 1024 || S1 < 32) return false;
-  ScatterArgs& sa = h.sa;
-  sa = ScatterArgs{};
-  sa.P = (int32_t)P;
-  sa.L = kStageRecs / P;
-  sa.lgL = 0;
-  while ((1u << sa.lgL) < sa.L) ++sa.lgL;
-  sa.B = n_cus;
-  sa.hm.d = (uint32_t)range;
-  sa.hm.S1 = S1;
-  sa.hm.S2 = S1;
-  sa.hm.R = 1;
-  sa.hm.d_rcp = (uint32_t)(((uint64_t)1 << 32) / sa.hm.d);
-  sa.hm.s1_rcp = (uint32_t)(((uint64_t)1 << 32) / S1);
-  sa.kmin = p.join_min;
-  // partial rows of spilled / heavy-hitter records: SUM, COUNT, COUNT of non-NULL values
-  sa.ns_int = 3;
-  sa.ops_packed = (uint32_t)SO_SUM_I | ((uint32_t)SO_COUNT << 4) | ((uint32_t)SO_COUNT_NN << 8);
-  sa.val_nullable = 1;  // the non-grouped SUM skips NULL_BIGINT even on a NOT NULL column
-  sa.null_bits = INT64_MIN;
-  int64_t chunk_rows = fv.total_rows > 0 ? fv.total_rows : 1;
-  if (chunk_rows > 0xfff00000ll) chunk_rows = 0xfff00000ll;
-  if (scratch_cap <= 0) scratch_cap = kDefaultScratchCap;
-  for (;;) {
-    const double per_run = (double)chunk_rows / ((double)P * sa.B);
-    uint64_t cap = (uint64_t)(per_run * 1.2 + 6.0 * __builtin_sqrt(per_run + 1.0)) + sa.L;
-    cap = (cap + sa.L - 1) / sa.L * sa.L;
-    const bool too_many = cap > 0x7fffffffull || (uint64_t)P * sa.B * cap >= ((uint64_t)1 << 32);
-    int64_t spill_cap = chunk_rows / 16;
-    if (spill_cap < (int64_t)kSpillMin) spill_cap = kSpillMin;
-    if (spill_cap > 0x7fffffffll) spill_cap = 0x7fffffffll;
-    h.rec_bytes = (int64_t)P * sa.B * (int64_t)cap * (int64_t)sizeof(Rec);
-    h.cnt_bytes = ((int64_t)P * sa.B * 4 + 255) & ~255ll;
-    const int64_t spill_bytes = 256 + spill_cap * 8 * (int64_t)(1 + sa.ns_int);
-    h.scratch_bytes = h.rec_bytes + h.cnt_bytes + spill_bytes;
-    if (!too_many && (h.scratch_bytes <= scratch_cap || chunk_rows <= fv.max_frag_rows)) {
-      sa.cap = (uint32_t)cap;
-      h.spill_cap = (uint32_t)spill_cap;
-      break;
-    }
-    if (chunk_rows <= fv.max_frag_rows) return false;
-    chunk_rows = (int64_t)(chunk_rows * 0.97);
-    if (chunk_rows < fv.max_frag_rows) chunk_rows = fv.max_frag_rows;
-  }
-  h.chunk_rows = chunk_rows;
-  {
-    const size_t fixed = kStageRecs * sizeof(Rec) + (size_t)P * 12 + 48 + (size_t)kHotSlots * (8 + 8 * (size_t)sa.ns_int);
-    sa.n_cand = 2048;
-    while (sa.n_cand > 64 && fixed + (size_t)sa.n_cand * 4 > 160 * 1024) sa.n_cand >>= 1;
-    h.lds1 = fixed + (size_t)sa.n_cand * 4;
-    if (h.lds1 > 160 * 1024) return false;
-  }
+  // (the one family whose chunks are not evened out)
+  if (!plan_direct_scatter(fv, n_cus, scratch_cap, P, range, S1, p.join_min, false, &h.sa, &h, &h.lds1)) return false;
+  const ScatterArgs& sa = h.sa;
   h.lds2 = (size_t)(S1 / 8) + 16 * 3 * 8;
   JoinPartArgs& ja = h.ja;
   ja.P = (int32_t)P;
@@ -2831,68 +2711,42 @@ hipError_t launch_join_partitioned(const DevPlan& p, const FragView& fv, int64_t
   JoinPartHost h;
   if (!make_join_part_plan(p, fv, n_cus, cap_bytes, &h)) return hipErrorInvalidValue;
   if (h.scratch_bytes + 64 > scratch_bytes) return hipErrorInvalidValue;
-  Rec* recs = (Rec*)scratch;
-  uint32_t* cnt = (uint32_t*)((char*)scratch + h.rec_bytes);
-  char* spill_base = (char*)scratch + h.rec_bytes + h.cnt_bytes;
-  SpillList sl{(uint32_t*)spill_base, (int64_t*)(spill_base + 256), d_err, h.spill_cap, 1 + h.sa.ns_int};
+  const ScratchCarve b(scratch, h.rec_bytes, h.cnt_bytes);
+  const Rec* recs = (const Rec*)b.recs;
+  const SpillList sl = spill_list(b, d_err, h.spill_cap, h.sa.ns_int);
   st->kernel_name = "k_part_scatter";
   st->variant = 2;
   st->n_launches = 0;
   (void)hipFuncSetAttribute((const void*)k_part_join, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds2);
-  RangeFilter flt = no_filter();
-  const int vcol = h.vcol < 0 ? 0 : h.vcol;
-  int ev_i = 0;
-  int f = 0;
-  while (f < fv.n_frags) {
-    int64_t rows = 0;
-    int f1 = f;
-    while (f1 < fv.n_frags && (f1 == f || rows + fv.h_num_rows[f1] <= h.chunk_rows)) {
-      rows += fv.h_num_rows[f1];
-      ++f1;
-    }
-    hipError_t e = hipMemsetAsync(spill_base, 0, 256, s);
+  TimedLaunches timed{st, s};
+  for (Chunk c = part_host::next_chunk(fv, 0, h.chunk_rows); c.nf > 0; c = part_host::next_chunk(fv, c.f0 + c.nf, h.chunk_rows)) {
+    hipError_t e = hipMemsetAsync(b.spill_base, 0, 256, s);
     if (e != hipSuccess) return e;
-    if (st->ev_pool && ev_i + 1 < st->n_ev) (void)hipEventRecord(st->ev_pool[ev_i], s);
-    const int8_t* const* cols = fv.d_cols + (size_t)f * fv.n_cols;
-    const int64_t* nrows = fv.d_num_rows + f;
-    if (h.vcol >= 0) {
-      (void)hipFuncSetAttribute((const void*)k_part_scatter<none_t, int64_t, 1>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds1);
-      hipLaunchKernelGGL((k_part_scatter<none_t, int64_t, 1>), dim3(h.sa.B), dim3(kPartBlock), h.lds1, s, cols,
-                         nrows, f1 - f, fv.n_cols, flt, p.join_col, vcol, h.sa, recs, cnt, sl);
-    } else {
-      (void)hipFuncSetAttribute((const void*)k_part_scatter<none_t, none_t, 1>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds1);
-      hipLaunchKernelGGL((k_part_scatter<none_t, none_t, 1>), dim3(h.sa.B), dim3(kPartBlock), h.lds1, s, cols,
-                         nrows, f1 - f, fv.n_cols, flt, p.join_col, vcol, h.sa, recs, cnt, sl);
-    }
-    e = hipGetLastError();
+    e = timed.run([&] { return launch_scatter_direct<1>(h.vcol, h.lds1, s, fv, c, p.join_col, h.sa, b, sl); });
     if (e != hipSuccess) return e;
-    if (st->ev_pool && ev_i + 1 < st->n_ev) {
-      (void)hipEventRecord(st->ev_pool[ev_i + 1], s);
-      ev_i += 2;
-    }
-    st->n_launches += 1;
     const int grid2 = h.ja.P < n_cus ? h.ja.P : n_cus;
-    hipLaunchKernelGGL(k_part_join, dim3(grid2), dim3(kPartBlock), h.lds2, s, h.ja, recs, cnt, out);
+    hipLaunchKernelGGL(k_part_join, dim3(grid2), dim3(kPartBlock), h.lds2, s, h.ja, recs, b.cnt, out);
     hipLaunchKernelGGL(k_join_spill, dim3(256), dim3(256), 0, s, h.ja, sl, out);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    f = f1;
   }
-  st->spill_counter32 = (uint32_t*)spill_base;
-  st->n_events_used = ev_i;
+  st->spill_counter32 = b.spill_count();
+  st->n_events_used = timed.ev_i;
   return hipSuccess;
 }
 
 // ---------------------------------------------------------------- payload probe: host side
+namespace {
+// 256 table entries per workgroup, at most 16 workgroups per CU
+unsigned payload_build_blocks(int64_t entries, int n_cus) {
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((entries + 255) / 256, (int64_t)n_cus * 16));
+}
+}  // namespace
+
 hipError_t launch_join_payload_build(const void* table, int hash_type, int64_t entries, const void* inner_col,
                                      uint32_t* cnt_k, int64_t* wsum_k, uint32_t* wnn_k, void* pay16, int64_t* pay8,
                                      int32_t* d_flags, int n_cus, hipStream_t s) {
-  int64_t blocks = (entries + 255) / 256;
-  if (blocks > (int64_t)n_cus * 16) blocks = (int64_t)n_cus * 16;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_join_payload, dim3((unsigned)blocks), dim3(256), 0, s, (const int32_t*)table, hash_type, entries,
+  hipLaunchKernelGGL(k_join_payload, dim3(payload_build_blocks(entries, n_cus)), dim3(256), 0, s, (const int32_t*)table, hash_type, entries,
                      (const int64_t*)inner_col, cnt_k, wsum_k, wnn_k, (Pay16*)pay16, pay8, d_flags);
   return hipGetLastError();
 }
@@ -2900,23 +2754,18 @@ hipError_t launch_join_payload_build(const void* table, int hash_type, int64_t e
 hipError_t launch_join_payload_keyed_build(const void* table, int hash_type, int64_t entries, const void* inner_col,
                                            int64_t* kkeys, void* pay16, int64_t* pay8, int32_t* d_flags, int n_cus,
                                            hipStream_t s) {
-  int64_t blocks = (entries + 255) / 256;
-  if (blocks > (int64_t)n_cus * 16) blocks = (int64_t)n_cus * 16;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(k_join_payload_keyed, dim3((unsigned)blocks), dim3(256), 0, s, (const int64_t*)table, hash_type,
+  hipLaunchKernelGGL(k_join_payload_keyed, dim3(payload_build_blocks(entries, n_cus)), dim3(256), 0, s, (const int64_t*)table, hash_type,
                      entries, (const int64_t*)inner_col, kkeys, (Pay16*)pay16, pay8, d_flags);
   return hipGetLastError();
 }
 
 namespace {
 
-struct ProbePartHost {
+struct ProbePartHost : RunSizes {
   ScatterArgs sa;
   ProbeArgs pa;
   ProbeFinish fin;
-  int64_t chunk_rows, rec_bytes, cnt_bytes, scratch_bytes;
   size_t lds1, lds2;
-  uint32_t spill_cap;
   int vcol;    // outer value column or -1
   int wcol;    // inner column or -1
   bool l2_mode;  // slices in L2 (k_part_probe_l2) instead of LDS (k_part_probe)
@@ -3009,61 +2858,8 @@ bool make_probe_plan(const DevPlan& p, const FragView& fv, const JoinPayloadView
     return false;
   }
   const uint32_t S2 = (uint32_t)((((uint64_t)S1 + R - 1) / R + 31) & ~(uint64_t)31);
-  ScatterArgs& sa = h.sa;
-  sa = ScatterArgs{};
-  sa.P = (int32_t)P;
-  sa.L = kStageRecs / P;
-  sa.lgL = 0;
-  while ((1u << sa.lgL) < sa.L) ++sa.lgL;
-  sa.B = n_cus;
-  sa.hm.d = (uint32_t)range;
-  sa.hm.S1 = S1;
-  sa.hm.S2 = S1;
-  sa.hm.R = 1;
-  sa.hm.d_rcp = (uint32_t)(((uint64_t)1 << 32) / sa.hm.d);
-  sa.hm.s1_rcp = (uint32_t)(((uint64_t)1 << 32) / S1);
-  sa.kmin = h.keyed ? 0 : p.join_min;
-  sa.ns_int = 3;  // spilled / heavy-hitter partial rows: SUM, COUNT, COUNT of non-NULL values
-  sa.ops_packed = (uint32_t)SO_SUM_I | ((uint32_t)SO_COUNT << 4) | ((uint32_t)SO_COUNT_NN << 8);
-  sa.val_nullable = 1;
-  sa.null_bits = INT64_MIN;
-  int64_t chunk_rows = fv.total_rows > 0 ? fv.total_rows : 1;
-  if (chunk_rows > 0xfff00000ll) chunk_rows = 0xfff00000ll;
-  if (scratch_cap <= 0) scratch_cap = kDefaultScratchCap;
-  for (;;) {
-    const double per_run = (double)chunk_rows / ((double)P * sa.B);
-    uint64_t cap = (uint64_t)(per_run * 1.2 + 6.0 * __builtin_sqrt(per_run + 1.0)) + sa.L;
-    cap = (cap + sa.L - 1) / sa.L * sa.L;
-    const bool too_many = cap > 0x7fffffffull || (uint64_t)P * sa.B * cap >= ((uint64_t)1 << 32);
-    int64_t spill_cap = chunk_rows / 16;
-    if (spill_cap < (int64_t)kSpillMin) spill_cap = kSpillMin;
-    if (spill_cap > 0x7fffffffll) spill_cap = 0x7fffffffll;
-    h.rec_bytes = (int64_t)P * sa.B * (int64_t)cap * (int64_t)sizeof(Rec);
-    h.cnt_bytes = ((int64_t)P * sa.B * 4 + 255) & ~255ll;
-    const int64_t spill_bytes = 256 + spill_cap * 8 * (int64_t)(1 + sa.ns_int);
-    h.scratch_bytes = h.rec_bytes + h.cnt_bytes + spill_bytes;
-    if (!too_many && (h.scratch_bytes <= scratch_cap || chunk_rows <= fv.max_frag_rows)) {
-      sa.cap = (uint32_t)cap;
-      h.spill_cap = (uint32_t)spill_cap;
-      break;
-    }
-    if (chunk_rows <= fv.max_frag_rows) return false;
-    chunk_rows = (int64_t)(chunk_rows * 0.97);
-    if (chunk_rows < fv.max_frag_rows) chunk_rows = fv.max_frag_rows;
-  }
-  if (fv.total_rows > chunk_rows) {
-    const int64_t n_chunks = (fv.total_rows + chunk_rows - 1) / chunk_rows;
-    const int64_t even = (fv.total_rows + n_chunks - 1) / n_chunks + fv.max_frag_rows;
-    if (even < chunk_rows) chunk_rows = even;
-  }
-  h.chunk_rows = chunk_rows;
-  {
-    const size_t fixed = kStageRecs * sizeof(Rec) + (size_t)P * 12 + 48 + (size_t)kHotSlots * (8 + 8 * (size_t)sa.ns_int);
-    sa.n_cand = 2048;
-    while (sa.n_cand > 64 && fixed + (size_t)sa.n_cand * 4 > 160 * 1024) sa.n_cand >>= 1;
-    h.lds1 = fixed + (size_t)sa.n_cand * 4;
-    if (h.lds1 > 160 * 1024) return false;
-  }
+  if (!plan_direct_scatter(fv, n_cus, scratch_cap, P, range, S1, h.keyed ? 0 : p.join_min, true, &h.sa, &h, &h.lds1)) return false;
+  const ScatterArgs& sa = h.sa;
   h.lds2 = h.l2_mode ? 0 : (size_t)S2 * entry_bytes + (size_t)16 * PA_N * 8 + 64;
   if (h.lds2 > 160 * 1024) return false;
   ProbeArgs& pa = h.pa;
@@ -3135,10 +2931,10 @@ hipError_t launch_join_probe(const DevPlan& p, const FragView& fv, const JoinPay
   ProbePartHost h;
   if (!make_probe_plan(p, fv, pay, n_cus, cap_bytes, &h)) return hipErrorInvalidValue;
   if (h.scratch_bytes + 64 + 512 > scratch_bytes) return hipErrorInvalidValue;
-  Rec* recs = (Rec*)scratch;
-  uint32_t* cnt = (uint32_t*)((char*)scratch + h.rec_bytes);
-  char* spill_base = (char*)scratch + h.rec_bytes + h.cnt_bytes;
-  SpillList sl{(uint32_t*)spill_base, (int64_t*)(spill_base + 256), d_err, h.spill_cap, 1 + h.sa.ns_int};
+  const ScratchCarve b(scratch, h.rec_bytes, h.cnt_bytes);
+  const Rec* recs = (const Rec*)b.recs;
+  const uint32_t* cnt = b.cnt;
+  const SpillList sl = spill_list(b, d_err, h.spill_cap, h.sa.ns_int);
   // accumulators live behind the spill list
   unsigned long long* acc = (unsigned long long*)((char*)scratch + h.scratch_bytes + 64 - 64);
   acc = (unsigned long long*)(((uintptr_t)acc + 63) & ~(uintptr_t)63);
@@ -3149,41 +2945,15 @@ hipError_t launch_join_probe(const DevPlan& p, const FragView& fv, const JoinPay
   st->variant = 3;
   st->n_launches = 0;
   (void)hipFuncSetAttribute((const void*)k_part_probe, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds2);
-  RangeFilter flt = no_filter();
-  const int vcol = h.vcol < 0 ? 0 : h.vcol;
-  int ev_i = 0;
-  int f = 0;
-  while (f < fv.n_frags) {
-    int64_t rows = 0;
-    int f1 = f;
-    while (f1 < fv.n_frags && (f1 == f || rows + fv.h_num_rows[f1] <= h.chunk_rows)) {
-      rows += fv.h_num_rows[f1];
-      ++f1;
-    }
-    e = hipMemsetAsync(spill_base, 0, 256, s);
+  TimedLaunches timed{st, s};
+  for (Chunk c = part_host::next_chunk(fv, 0, h.chunk_rows); c.nf > 0; c = part_host::next_chunk(fv, c.f0 + c.nf, h.chunk_rows)) {
+    e = hipMemsetAsync(b.spill_base, 0, 256, s);
     if (e != hipSuccess) return e;
-    if (st->ev_pool && ev_i + 1 < st->n_ev) (void)hipEventRecord(st->ev_pool[ev_i], s);
-    const int8_t* const* cols = fv.d_cols + (size_t)f * fv.n_cols;
-    const int64_t* nrows = fv.d_num_rows + f;
-    auto scatter = [&](auto kern) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h.lds1);
-      hipLaunchKernelGGL(kern, dim3(h.sa.B), dim3(kPartBlock), h.lds1, s, cols, nrows, f1 - f, fv.n_cols, flt, p.join_col,
-                         vcol, h.sa, recs, cnt, sl);
-    };
-    if (h.keyed) {
-      if (h.vcol >= 0) scatter(k_part_scatter<none_t, int64_t, 2>);
-      else scatter(k_part_scatter<none_t, none_t, 2>);
-    } else {
-      if (h.vcol >= 0) scatter(k_part_scatter<none_t, int64_t, 1>);
-      else scatter(k_part_scatter<none_t, none_t, 1>);
-    }
-    e = hipGetLastError();
+    e = timed.run([&] {
+      return h.keyed ? launch_scatter_direct<2>(h.vcol, h.lds1, s, fv, c, p.join_col, h.sa, b, sl)
+                     : launch_scatter_direct<1>(h.vcol, h.lds1, s, fv, c, p.join_col, h.sa, b, sl);
+    });
     if (e != hipSuccess) return e;
-    if (st->ev_pool && ev_i + 1 < st->n_ev) {
-      (void)hipEventRecord(st->ev_pool[ev_i + 1], s);
-      ev_i += 2;
-    }
-    st->n_launches += 1;
     unsigned int* pace = (h.l2_mode && !(tune_knobs().flags & MI355Q_OPT_PROBE_NO_PACING)) ? (unsigned int*)(acc2 + 2) : nullptr;
     if (pace) {
       e = hipMemsetAsync(pace, 0, 64, s);
@@ -3216,7 +2986,6 @@ hipError_t launch_join_probe(const DevPlan& p, const FragView& fv, const JoinPay
     hipLaunchKernelGGL(k_probe_spill, dim3(256), dim3(256), 0, s, h.pa, sl, acc);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    f = f1;
   }
   if (h.fin.left && h.vcol >= 0) {
     int64_t want = (fv.total_rows / 4 + kBlock - 1) / kBlock;
@@ -3228,8 +2997,8 @@ hipError_t launch_join_probe(const DevPlan& p, const FragView& fv, const JoinPay
   hipLaunchKernelGGL(k_probe_finish, dim3(1), dim3(64), 0, s, h.fin, acc, acc2, out);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  st->spill_counter32 = (uint32_t*)spill_base;
-  st->n_events_used = ev_i;
+  st->spill_counter32 = b.spill_count();
+  st->n_events_used = timed.ev_i;
   return hipSuccess;
 }
 

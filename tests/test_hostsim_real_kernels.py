@@ -1198,3 +1198,113 @@ def test_typed_lds_member_count_only_under_filters(sim, oracle, shape, baseline,
         assert rs.report.variant == (4 if member == "generic" else 5), rs.report.variant
     else:
         assert name == "k_perfect_lds" and not baseline and shape == "two_bounds_one_column", (name, shape)
+
+
+# ---- plans of the partitioned families (part_host.h: size_runs): routes, scratch sizes and reports, pinned -----------------
+def _plan_shapes():
+    return {"1x1e5": [100_000], "3x_odd": [40_001, 80_003, 120_005], "4x32M": [32_000_000] * 4, "32x1e9": [32_000_000] * 31 + [8_000_000],
+            "7x3e9_uneven": [100_000_000, 900_000_000, 17, 650_000_003, 400_000_000, 1, 949_999_979], "64x1e10": [156_250_000] * 64,
+            "3x1e10_big_frags": [4_000_000_000, 3_500_000_000, 2_500_000_000]}
+
+
+def _explain_opts(sim, ra, frag_rows, inner_rows=0, kernel_variant=2, scratch_bytes=0, tune_cus=0, tune_overlap_cus=0, flags=0):
+    """mi355q_explain with the tuning options of a step: (route, scratch bytes)"""
+    from heavydb_amd.executor import Executor, FetchResult
+    plan = ra.to_plan()
+    fr = FetchResult([[0] * plan.n_cols for _ in frag_rows], list(frag_rows), [0] * 8 if inner_rows else [], inner_rows)
+    inp, keep = fr.to_c(plan.n_cols)
+    opts = Executor(0)._opts(None, None, False, kernel_variant, scratch_bytes, flags=flags)
+    opts.tune_cus, opts.tune_overlap_cus = tune_cus, tune_overlap_cus
+    buf, got = C.create_string_buffer(512), C.c_int64()
+    assert sim.mi355q_explain(C.byref(plan), C.byref(inp), C.byref(opts), buf, 512, C.byref(got)) == 0
+    return buf.value.decode(), got.value
+
+
+def _groupby_plan(sim, entries, tset, shape, **o):
+    from heavydb_amd.executor import ExpressionRange, InputColDescriptor, Qual, RelAlgExecutionUnit, TargetExpr
+    if tset == 0:
+        descs = [InputColDescriptor(capi.INT64, False, ExpressionRange(False)), InputColDescriptor(capi.INT64, False, ExpressionRange(True, -50, 49))]
+        targets, quals = [TargetExpr(capi.PROJECT_KEY), TargetExpr(capi.COUNT), TargetExpr(capi.SUM, 1), TargetExpr(capi.MIN, 1)], []
+    else:
+        descs = [InputColDescriptor(capi.INT64, False, ExpressionRange(False)), InputColDescriptor(capi.DOUBLE, True, ExpressionRange(True, 0, 0, True, 0.0, 1000.0)),
+                 InputColDescriptor(capi.INT32, False, ExpressionRange(True, 0, 2**31 - 1))]
+        targets, quals = [TargetExpr(capi.PROJECT_KEY), TargetExpr(capi.COUNT), TargetExpr(capi.AVG, 1)], [Qual(2, capi.LT, 2**30)]
+    rows = _plan_shapes()[shape]
+    ra = RelAlgExecutionUnit(descs, targets, quals, [0], max_groups_buffer_entry_guess=entries, num_tuples=sum(rows))
+    return _explain_opts(sim, ra, rows, **o)
+
+
+def _idx_plan(sim, card, nv, hi, shape, **o):
+    from heavydb_amd.executor import ExpressionRange, InputColDescriptor, RelAlgExecutionUnit, TargetExpr
+    vd = InputColDescriptor(capi.INT32, True, ExpressionRange(hi > 0, 1, max(hi, 1), True))
+    descs = [InputColDescriptor(capi.INT32, True, ExpressionRange(True, 1, card, False))] + [vd] * nv
+    targets = [TargetExpr(capi.PROJECT_KEY), TargetExpr(capi.COUNT)] + [TargetExpr([capi.SUM, capi.MIN, capi.AVG][v], 1 + v) for v in range(nv)]
+    rows = _plan_shapes()[shape]
+    ra = RelAlgExecutionUnit(descs, targets, [], [0], max_groups_buffer_entry_guess=2 * card, num_tuples=sum(rows))
+    return _explain_opts(sim, ra, rows, **o)
+
+
+def _join_plan(sim, lg, with_sum, shape, **o):
+    from heavydb_amd.executor import ExpressionRange, HashJoin, InputColDescriptor, RelAlgExecutionUnit, TargetExpr
+    m = 1 << lg
+    dim = flow._aligned(np.random.default_rng(3).permutation(np.arange(0, m, dtype=np.int64)))
+    hj = HashJoin.getInstance(dim.ctypes.data, m, capi.INT64, ExpressionRange(True, 0, m - 1))
+    descs = [InputColDescriptor(capi.INT64, False, ExpressionRange(True, 0, m - 1)), InputColDescriptor(capi.INT64, False, ExpressionRange(True, -10**9, 10**9))]
+    inner = [InputColDescriptor(capi.INT64, False, ExpressionRange(True, 0, m - 1))]
+    ra = RelAlgExecutionUnit(descs, [TargetExpr(capi.COUNT)] + ([TargetExpr(capi.SUM, 1)] if with_sum else []), inner_col_descs=inner,
+                             join_outer_col=0, join_table=hj)
+    return _explain_opts(sim, ra, _plan_shapes()[shape], inner_rows=m, **o)
+
+
+def _probe_report(sim, keyed, scratch_bytes):
+    """the payload probe over seven fragments: (kernel_name, variant, n_launches, spilled_rows)"""
+    from heavydb_amd.executor import Executor, ExpressionRange, InputColDescriptor, RelAlgExecutionUnit, TargetExpr
+    rng = np.random.default_rng(41)
+    n, m, mul = 70_003, 1 << 14, 1000003 if keyed else 1
+    dim = rng.permutation(m).astype(np.int64) * mul
+    w = rng.integers(-1000, 1000, m).astype(np.int64)
+    k = rng.integers(-100, m + 100, n).astype(np.int64) * mul
+    k[rng.random(n) < 0.3] = 777 * mul
+    v = rng.integers(-10**6, 10**6, n).astype(np.int64)
+    descs = [InputColDescriptor(capi.INT64, False, ExpressionRange(True, -100 * mul, (m + 99) * mul)), InputColDescriptor(capi.INT64, False, ExpressionRange(True, -10**6, 10**6))]
+    inner = [InputColDescriptor(capi.INT64, False, ExpressionRange(True, 0, (m - 1) * mul)), InputColDescriptor(capi.INT64, False, ExpressionRange(True, -1000, 999))]
+    ra = RelAlgExecutionUnit(descs, [TargetExpr(capi.COUNT), TargetExpr(capi.SUM, 1, 1), TargetExpr(capi.SUM, 1)], inner_col_descs=inner, join_outer_col=0)
+    cuts = [0] + [(n * i // 7) & ~3 for i in range(1, 7)] + [n]
+    case = cases_mod.Case("probe_plan", ra, [[k[a:b], v[a:b]] for a, b in zip(cuts[:-1], cuts[1:])], [dim, w], dim, capi.INT64,
+                          ExpressionRange(True, 0, (m - 1) * mul), False)
+    hj, keep = flow._build_join(case)
+    case.ra.join_table = hj
+    r = Executor(0).executeWorkUnit(case.ra, flow._fetch_result(case), allow_retry=False, kernel_variant=3, scratch_bytes=scratch_bytes).report
+    return r.kernel_name.decode(), r.variant, r.n_launches, r.spilled_rows
+
+
+GB = 1 << 30
+PINNED_PLANS = [
+    # (what, arguments, options) -> the tuple the commit before the shared run sizing gave
+    ("groupby", (1 << 24, 0, "4x32M"), dict(tune_cus=64, scratch_bytes=8 << 20), ('k_part_scatter + k_part_aggregate', 799068480)),
+    ("groupby", (1 << 24, 0, "4x32M"), dict(tune_cus=64, scratch_bytes=8 << 20, tune_overlap_cus=4), ('k_part_scatter + k_part_aggregate', 1568744000)),
+    ("groupby", (1 << 28, 1, "64x1e10"), dict(tune_cus=256, scratch_bytes=16 * GB), ('k_baseline_direct', 0)),
+    ("groupby", (1 << 28, 1, "64x1e10"), dict(tune_cus=256, scratch_bytes=16 * GB, tune_overlap_cus=4), ('k_baseline_direct', 0)),
+    ("groupby", (1 << 17, 1, "1x1e5"), dict(tune_cus=8), ('k_part_scatter + k_part_aggregate', 138433344)),
+    ("groupby", (1 << 31, 0, "64x1e10"), dict(tune_cus=256), ('k_baseline_direct', 0)),   # refused: another family takes the step
+    ("idx", (3_000_000, 1, 10, "32x1e9"), dict(tune_cus=256, scratch_bytes=GB), ('k_idx_scatter + k_idx_aggregate', 982572448)),
+    ("idx", ((1 << 24) - 5, 2, 10, "3x1e10_big_frags"), dict(tune_cus=256), ('k_idx_scatter + k_idx_aggregate', 23338920256)),
+    ("idx", (150_000, 0, 10, "3x_odd"), dict(tune_cus=8, scratch_bytes=8 << 20), ('8-byte-slot twin + k_narrow_slots > k_idx_scatter + k_idx_aggregate', 18875200)),
+    ("idx", (40_000_000, 1, 0, "64x1e10"), dict(tune_cus=64, scratch_bytes=16 * GB, flags=capi.OPT_NO_IDX_PACK), ('k_pack_keys (bit-packed key) > k_baseline_direct > k_unpack_emit', 0)),
+    ("join", (20, True, "64x1e10"), dict(tune_cus=256, scratch_bytes=16 * GB), ('k_part_scatter + k_part_join', 17091434304)),
+    ("join", (17, False, "3x_odd"), dict(tune_cus=8, scratch_bytes=8 << 20), ('k_part_scatter + k_part_join', 138413376)),
+    ("join", (20, True, "7x3e9_uneven"), dict(tune_cus=256, scratch_bytes=GB), ('k_part_scatter + k_part_join', 20189263872)),
+    ("probe", (False,), dict(scratch_bytes=1 << 20), ('k_part_scatter', 3, 7, 4)),
+    ("probe", (True,), dict(scratch_bytes=1 << 20), ('k_part_scatter', 3, 7, 4)),
+]
+
+
+@pytest.mark.parametrize("idx", range(len(PINNED_PLANS)))
+def test_partitioned_plans_are_the_pinned_ones(sim, idx):
+    """Route and scratch size (mi355q_explain) of the hash-partitioned GROUP BY, sequential, chunked and overlapped, of the
+    index-partitioned GROUP BY and of the radix join at 8 - 256 CUs, under several scratch caps, up to 10^10 rows in 64
+    fragments; report of the payload probe (perfect and keyed) in several chunks.  The values are those of the four
+    hand-written sizing loops that part_host.h's size_runs replaced."""
+    what, args, opts, want = PINNED_PLANS[idx]
+    got = {"groupby": _groupby_plan, "idx": _idx_plan, "join": _join_plan, "probe": _probe_report}[what](sim, *args, **opts)
+    assert got == want, (what, args, opts, got)

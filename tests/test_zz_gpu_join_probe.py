@@ -255,3 +255,58 @@ def test_grouped_join_through_the_gather_route_at_16m_rows(torch_cuda, oracle, l
     assert code == 0
     compare_buffers(q, want, rs.getStorage())
     compare_buffers(q, want, row.getStorage())
+
+
+@pytest.mark.parametrize("member", ["radix_join", "probe_perfect", "probe_keyed"])
+def test_join_members_one_fragment_per_chunk(torch_cuda, oracle, member):
+    """The chunk walk of the radix join (kernel_variant 2) and of the payload probe (kernel_variant 3, perfect and keyed
+    table): four outer fragments of unequal sizes, none a multiple of four rows, under a 1 MB scratch cap, where the
+    planner is at its floor of whole fragments per chunk (the runs of one chunk alone exceed the cap).  A table of 2^18
+    entries: every partition holds keys.  Every slot is the oracle's, and a second run of the step gives the same."""
+    from heavydb_amd.executor import (Executor, ExpressionRange, FetchResult, HashJoin, InputColDescriptor,
+                                      RelAlgExecutionUnit, TargetExpr)
+    torch = torch_cuda
+    rng = np.random.default_rng(2024)
+    keyed = member == "probe_keyed"
+    mul = 1000003 if keyed else 1    # sparse keys: too wide a range for a perfect table -> keyed
+    m = 1 << 17 if keyed else 1 << 18
+    dim = rng.permutation(np.arange(5000, 5000 + m, dtype=np.int64)) * mul
+    w = rng.integers(-10**6, 10**6, m).astype(np.int64)
+    dmin, dmax = int(dim.min()), int(dim.max())
+    dk, dw = torch.from_numpy(dim).cuda(), torch.from_numpy(w).cuda()
+    hj = HashJoin.getInstance(int(dk.data_ptr()), m, capi.INT64, ExpressionRange(True, dmin, dmax))
+    assert hj.info()["hash_type"] == (1 if keyed else 0)
+    sizes = [40_001, 80_003, 120_005, 65_537]
+    n = sum(sizes)
+    k = rng.integers(dmin // mul - m // 8, dmax // mul + m // 8, n).astype(np.int64) * mul   # four in five match
+    k[rng.random(n) < 0.05] = dim[777]
+    v = rng.integers(-10**9, 10**9, n).astype(np.int64)
+    v[rng.random(n) < 0.02] = -2**63
+    descs = [InputColDescriptor(capi.INT64, False, ExpressionRange(True, dmin - (m // 8) * mul, dmax + (m // 8) * mul)),
+             InputColDescriptor(capi.INT64, False, ExpressionRange(True, -10**9, 10**9))]
+    inner = [InputColDescriptor(capi.INT64, False, ExpressionRange(True, dmin, dmax)),
+             InputColDescriptor(capi.INT64, False, ExpressionRange(True, -10**6, 10**6))]
+    if member == "radix_join":
+        targets, variant = [TargetExpr(capi.COUNT), TargetExpr(capi.SUM, 1)], 2
+    else:
+        targets, variant = [TargetExpr(capi.COUNT), TargetExpr(capi.SUM, 1), TargetExpr(capi.SUM, 1, 1), TargetExpr(capi.COUNT, 1, 1)], 3
+    ra = RelAlgExecutionUnit(descs, targets, inner_col_descs=inner, join_outer_col=0, join_table=hj)
+    cuts = np.concatenate([[0], np.cumsum(sizes)])
+    host = [[k[a:b], v[a:b]] for a, b in zip(cuts[:-1], cuts[1:])]
+    dev = [[torch.from_numpy(c).cuda() for c in f] for f in host]      # a tensor per fragment: every one 16-byte aligned
+    fr = FetchResult([[int(t.data_ptr()) for t in f] for f in dev], sizes, [int(dk.data_ptr()), int(dw.data_ptr())], m,
+                     keepalive=[t for f in dev for t in f] + [dk, dw])
+    ex = Executor(0)
+    rs = ex.executeWorkUnit(ra, fr, allow_retry=False, kernel_variant=variant, scratch_bytes=1 << 20)
+    assert rs.report.variant == variant and rs.report.kernel_name.decode() == "k_part_scatter", \
+        (rs.report.variant, rs.report.kernel_name)
+    assert rs.report.n_launches >= 2, rs.report.n_launches
+    oj = oracle.OracleJoin(dim, capi.INT64, dmin, dmax)
+    ra.join_table = None
+    q, want, code = oracle.execute(ra.to_plan(), host, [dim, w], oj, n_threads=2)
+    ra.join_table = hj
+    assert code == 0
+    compare_buffers(q, want, rs.getStorage())
+    again = ex.executeWorkUnit(ra, fr, allow_retry=False, kernel_variant=variant, scratch_bytes=1 << 20)
+    assert again.report.n_launches == rs.report.n_launches
+    assert np.array_equal(again.getStorage(), rs.getStorage())

@@ -218,39 +218,24 @@ int32_t mi355q_release_workspace(int32_t device_id) {
   // a step left in flight by mi355q_execute_async still points into the workspace (error words, column table,
   // events, the launch stream): finish it before anything is freed
   drain_inflight(ctx);
-  if (ctx.scratch) (void)hipFree(ctx.scratch);
+  ctx.scratch.release();
   if (ctx.meta) (void)hipFree(ctx.meta);
+  ctx.meta = nullptr;
+  ctx.meta_bytes = 0;
   if (ctx.h_meta) (void)hipHostFree(ctx.h_meta);
   ctx.h_meta = nullptr;
-  if (ctx.aux) (void)hipFree(ctx.aux);
-  ctx.aux = nullptr;
-  ctx.aux_bytes = 0;
-  if (ctx.wide) (void)hipFree(ctx.wide);
-  ctx.wide = nullptr;
-  ctx.wide_bytes = 0;
-  if (ctx.proj) (void)hipFree(ctx.proj);
-  ctx.proj = nullptr;
-  ctx.proj_bytes = 0;
-  if (ctx.gather) (void)hipFree(ctx.gather);
-  ctx.gather = nullptr;
-  ctx.gather_bytes = 0;
-  if (ctx.lattice) (void)hipFree(ctx.lattice);
-  ctx.lattice = nullptr;
-  ctx.lattice_bytes = 0;
+  ctx.aux.release();
+  ctx.wide.release();
+  ctx.proj.release();
+  ctx.gather.release();
+  ctx.lattice.release();
   if (ctx.bf_table) (void)hipFree(ctx.bf_table);
   ctx.bf_table = nullptr;
-  if (ctx.maskws) (void)hipFree(ctx.maskws);
-  ctx.maskws = nullptr;
-  ctx.maskws_bytes = 0;
-  if (ctx.projws) (void)hipFree(ctx.projws);
-  ctx.projws = nullptr;
-  ctx.projws_bytes = 0;
+  ctx.maskws.release();
+  ctx.projws.release();
   if (ctx.stream) (void)hipStreamDestroy(ctx.stream);
   ctx.stream = nullptr;
   for (hipEvent_t e : ctx.events) (void)hipEventDestroy(e);
-  ctx.scratch = ctx.meta = nullptr;
-  ctx.scratch_bytes = 0;
-  ctx.meta_bytes = 0;
   ctx.events.clear();
   return MI355Q_OK;
 }
@@ -280,6 +265,24 @@ constexpr int32_t kRetryNoLds = INT32_MIN + 8;  // internal: the LDS group-by ra
 // next call on the device) runs it.  Everything it touches is owned here: the caller's host arrays may be
 // gone by then.
 enum StepKind { K_GENERIC, K_SCAN_COUNT, K_PERFECT_LDS, K_BASELINE_FAST, K_JOIN_SUM, K_JOIN_PART, K_JOIN_PROBE, K_SCAN_AGG, K_LDS_GROUPBY, K_IDX_PART };
+
+// the family as mi355q_explain names it (the partitioned GROUP BY by the member its plan picks)
+const char* family_name(StepKind kind, const DevPlan& d, const FragView& fv, int kernel_variant, int n_cus) {
+  switch (kind) {
+    case K_SCAN_COUNT: return "k_scan_count";
+    case K_SCAN_AGG: return "k_scan_agg";
+    case K_PERFECT_LDS: return "k_perfect_lds";
+    case K_LDS_GROUPBY: return "k_groupby_lds";
+    case K_JOIN_SUM: return "k_join_sum";
+    case K_JOIN_PART: return "k_part_scatter + k_part_join";
+    case K_JOIN_PROBE: return "k_part_scatter + k_part_probe";
+    case K_IDX_PART: return "k_idx_scatter + k_idx_aggregate";
+    case K_BASELINE_FAST:
+      return fv.n_frags > 0 && baseline_fast_variant(d, fv, kernel_variant, n_cus) == 2 ? "k_part_scatter + k_part_aggregate" : "k_baseline_direct";
+    default: return "k_generic";
+  }
+}
+
 struct TailState {
   mi355q_qmd q;
   DevPlan d;
@@ -311,6 +314,18 @@ struct KnobScope {  // the thread's knobs for the duration of finish_step
   ~KnobScope() { set_tune_knobs(saved); }
 };
 
+// a partitioned member ran out of spill space (extreme skew): the step again, into the same table, with the member
+// `launch` enqueues — error words cleared, table initialised, launched, the words read back, synchronised
+template <class Launch>
+int32_t redo_step(TailState& t, int32_t (&h_err)[2], Launch&& launch) {
+  HIP_TRY(hipMemsetAsync(t.d_err, 0, 64, t.s));
+  HIP_TRY(launch_init_buffer(t.res->buf, t.q.entry_count, make_row_init(t.q), t.s));
+  HIP_TRY(launch());
+  HIP_TRY(hipMemcpyAsync(h_err, t.d_err, sizeof(h_err), hipMemcpyDeviceToHost, t.s));
+  HIP_TRY(hipStreamSynchronize(t.s));
+  return MI355Q_OK;
+}
+
 int32_t finish_step(TailState& t, mi355q_exec_report* report) {
   KnobScope knob_scope(t.knobs);
   hipStream_t s = t.s;
@@ -341,36 +356,23 @@ int32_t finish_step(TailState& t, mi355q_exec_report* report) {
   st.spilled_rows = (int64_t)h_spills;
   if (h_err[1] && (t.kind == K_JOIN_PART || t.kind == K_JOIN_PROBE || t.kind == K_BASELINE_FAST)) t.recomputed = true;
   if (h_err[1] && t.trace) std::fprintf(stderr, "[mi355q] partitioned family gave up (code %d, spills %u): re-running with the direct kernel\n", h_err[1], h_spills);
-  if (h_err[1] && t.kind == K_JOIN_PART) {
-    // the partitioned probe ran out of spill space (extreme skew): redo with the direct probe
-    HIP_TRY(hipMemsetAsync(t.d_err, 0, 64, s));
-    HIP_TRY(launch_init_buffer(t.res->buf, q.entry_count, make_row_init(q), s));
-    HIP_TRY(launch_join_sum(d, fv, t.res->buf, t.n_cus, s, &st));
-    HIP_TRY(hipMemcpyAsync(h_err, t.d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
-  if (h_err[1] && t.kind == K_JOIN_PROBE) {
-    // the payload probe ran out of spill space (extreme skew): redo the step with the row kernel
-    HIP_TRY(hipMemsetAsync(t.d_err, 0, 64, s));
-    HIP_TRY(launch_init_buffer(t.res->buf, q.entry_count, make_row_init(q), s));
-    HIP_TRY(launch_generic(d, q.idx_target_as_key, make_row_init(q), t.d_cols, t.d_rows, t.nf, t.max_frag_rows, t.res->buf,
-                           t.d_err, t.n_cus, s));
-    st.kernel_name = "k_generic";
-    HIP_TRY(hipMemcpyAsync(h_err, t.d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  }
   // more groups than an LDS replica holds (a baseline table: the group count is only known now): the caller plans
   // the step again without that member (packed route / partitioned family / row kernel, whatever applies)
   if (h_err[1] && t.kind == K_LDS_GROUPBY) return kRetryNoLds;
   if (h_err[1] && t.kind == K_IDX_PART) return kRetryNoIdx;
-  if (h_err[1] && t.kind == K_BASELINE_FAST) {
-    // the partitioned family ran out of spill space (extreme skew): redo the step with the
-    // direct-atomic member of the same family
-    HIP_TRY(hipMemsetAsync(t.d_err, 0, 64, s));
-    HIP_TRY(launch_init_buffer(t.res->buf, q.entry_count, make_row_init(q), s));
-    HIP_TRY(launch_baseline_fast(d, fv, t.res->buf, t.d_err, nullptr, 0, 0, 1, t.n_cus, s, &st));
-    HIP_TRY(hipMemcpyAsync(h_err, t.d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+  if (h_err[1] && t.kind == K_JOIN_PART) {  // the partitioned probe: redo with the direct probe
+    if (int32_t e = redo_step(t, h_err, [&] { return launch_join_sum(d, fv, t.res->buf, t.n_cus, s, &st); })) return e;
+  } else if (h_err[1] && t.kind == K_JOIN_PROBE) {  // the payload probe: redo with the row kernel, which the report then names
+    if (int32_t e = redo_step(t, h_err, [&] {
+          const hipError_t he = launch_generic(d, q.idx_target_as_key, make_row_init(q), t.d_cols, t.d_rows, t.nf, t.max_frag_rows,
+                                               t.res->buf, t.d_err, t.n_cus, s);
+          if (he == hipSuccess) st.kernel_name = "k_generic";
+          return he;
+        }))
+      return e;
+  } else if (h_err[1] && t.kind == K_BASELINE_FAST) {  // the partitioned GROUP BY: redo with the direct-atomic member of the same family
+    if (int32_t e = redo_step(t, h_err, [&] { return launch_baseline_fast(d, fv, t.res->buf, t.d_err, nullptr, 0, 0, 1, t.n_cus, s, &st); }))
+      return e;
   }
   if (report) {
     std::memset(report, 0, sizeof(*report));
@@ -436,17 +438,42 @@ int32_t mi355q_execute(const mi355q_plan* plan, const mi355q_inputs* in,
   return execute_impl(plan, in, opts, out, report, nullptr);
 }
 
-int32_t mi355q_reserve_workspace(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options* opts,
-                                 int64_t* reserved_bytes) {
-  if (!plan || !in) return MI355Q_ERR_INVALID_PLAN;
-  int64_t bytes = 0;
-  // the planner looks at the pointer table for alignment only: a table of NULLs stands in for it
+}  // extern "C"
+
+namespace {
+
+// mi355q_reserve_workspace / mi355q_explain: the step planned in RESERVE mode.  The planner looks at the pointer table
+// for alignment only: a table of NULLs stands in for it (16-byte aligned chunks assumed)
+int32_t plan_without_columns(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options* opts, int64_t* bytes) {
   std::vector<const void*> none((size_t)std::max(1, in->n_frags * std::max(plan->n_cols + plan->n_exprs + 1, 1)), nullptr);  // (+ 1: the row mask of a compiled filter, execute_masked)
   mi355q_inputs in2 = *in;
   in2.col_buffers = none.data();
   mi355q_result* r = nullptr;
-  const int32_t e = execute_impl(plan, &in2, opts, &r, nullptr, nullptr, &bytes);
+  const int32_t e = execute_impl(plan, &in2, opts, &r, nullptr, nullptr, bytes);
   if (r) mi355q_result_free(r);
+  return e;
+}
+
+struct ExplainScope {  // the thread plans only and writes its route down, for the duration of mi355q_explain
+  explicit ExplainScope(std::string* text) {
+    t_route = text;
+    t_plan_only = true;
+  }
+  ~ExplainScope() {
+    t_route = nullptr;
+    t_plan_only = false;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+int32_t mi355q_reserve_workspace(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options* opts,
+                                 int64_t* reserved_bytes) {
+  if (!plan || !in) return MI355Q_ERR_INVALID_PLAN;
+  int64_t bytes = 0;
+  const int32_t e = plan_without_columns(plan, in, opts, &bytes);
   if (reserved_bytes) *reserved_bytes = bytes;
   return e;
 }
@@ -463,19 +490,9 @@ int32_t mi355q_explain(const mi355q_plan* plan, const mi355q_inputs* in, const m
   std::string text;
   int32_t e;
   try {
-    std::vector<const void*> none((size_t)std::max(1, in->n_frags * std::max(plan->n_cols + plan->n_exprs + 1, 1)), nullptr);  // (+ 1: the row mask of a compiled filter, execute_masked)
-    mi355q_inputs in2 = *in;
-    in2.col_buffers = none.data();  // (16-byte aligned chunks assumed, as mi355q_reserve_workspace does)
-    mi355q_result* r = nullptr;
-    t_route = &text;
-    t_plan_only = true;
-    e = execute_impl(plan, &in2, opts, &r, nullptr, nullptr, &bytes);
-    t_route = nullptr;
-    t_plan_only = false;
-    if (r) mi355q_result_free(r);
+    ExplainScope scope(&text);
+    e = plan_without_columns(plan, in, opts, &bytes);
   } catch (...) {
-    t_route = nullptr;
-    t_plan_only = false;
     return MI355Q_ERR_OUT_OF_CPU_MEM;
   }
   if (route && route_len > 0) std::snprintf(route, (size_t)route_len, "%s", text.c_str());
@@ -528,6 +545,283 @@ int32_t mi355q_wait(mi355q_pending* p, mi355q_exec_report* report) {
 
 }  // extern "C"
 
+int32_t mq::api::upload_frag_table(DeviceCtx& ctx, const mi355q_inputs& in, int nc, void* callers_stream, FragUpload mode,
+                                   FragTable* ft) {
+  const int nf = in.n_frags;
+  const size_t ptr_bytes = sizeof(void*) * (size_t)std::max(1, nf * nc);
+  const size_t rows_bytes = sizeof(int64_t) * (size_t)std::max(1, nf);
+  const size_t tab_bytes = ptr_bytes + rows_bytes;
+  const size_t meta_bytes = tab_bytes + 64;
+  if (ctx.meta_bytes < meta_bytes) {
+    if (ctx.meta) (void)hipFree(ctx.meta);
+    ctx.meta = nullptr;
+    ctx.meta_bytes = 0;
+    if (ctx.h_meta) (void)hipHostFree(ctx.h_meta);
+    ctx.h_meta = nullptr;
+    ctx.h_ret_dev = nullptr;
+    ctx.meta_shadow.clear();
+    HIP_TRY(hipMalloc(&ctx.meta, meta_bytes * 2));
+    HIP_TRY(hipHostMalloc((void**)&ctx.h_meta, meta_bytes * 2 + 64, hipHostMallocDefault));
+    ctx.meta_bytes = meta_bytes * 2;
+  }
+  if (!ctx.h_ret_dev && ctx.h_meta) {
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, ctx.h_meta + ctx.meta_bytes, 0) == hipSuccess) ctx.h_ret_dev = (int32_t*)dp;
+    else (void)hipGetLastError();
+  }
+  if (int32_t e = launch_stream(ctx, callers_stream, &ft->s)) return e;
+  char* mp = (char*)ctx.meta;
+  char* hm = ctx.h_meta;
+  ft->d_cols = (const int8_t* const*)mp;
+  ft->d_rows = (const int64_t*)(mp + ptr_bytes);
+  ft->d_err = (int32_t*)(mp + tab_bytes);
+  // the same table as the last upload, its error words untouched since: nothing to send
+  const bool same = mode == FragUpload::kSkipUnchanged && nf > 0 && ctx.meta_err_clean && ctx.meta_shadow.size() == tab_bytes &&
+                    !std::memcmp(ctx.meta_shadow.data(), in.col_buffers, sizeof(void*) * (size_t)(nf * nc)) &&
+                    !std::memcmp(ctx.meta_shadow.data() + ptr_bytes, in.num_rows, sizeof(int64_t) * (size_t)nf);
+  if (mode == FragUpload::kAlways) {
+    ctx.meta_shadow.clear();
+    ctx.meta_err_clean = false;
+  }
+  if (mode != FragUpload::kNone && !same) {
+    // one copy out of pinned memory: column table | row counts | zeroed error words (the synchronous step of a 60 us scan
+    // used to spend ~90 us on a memset and two copies out of pageable memory, each staged by the driver; VERDICT r03 weak #6)
+    if (nf > 0) {
+      std::memcpy(hm, in.col_buffers, sizeof(void*) * (size_t)(nf * nc));
+      std::memcpy(hm + ptr_bytes, in.num_rows, sizeof(int64_t) * (size_t)nf);
+    }
+    std::memset(hm + tab_bytes, 0, 64);
+    const size_t lo = nf > 0 ? 0 : tab_bytes;
+    HIP_TRY(hipMemcpyAsync(mp + lo, hm + lo, tab_bytes + 64 - lo, hipMemcpyHostToDevice, ft->s));
+    if (mode == FragUpload::kSkipUnchanged) {
+      if (nf > 0) ctx.meta_shadow.assign(hm, hm + tab_bytes);
+      else ctx.meta_shadow.clear();
+    }
+  }
+  ctx.meta_err_clean = false;  // (until a step's words have been read back as zeros: execute_impl)
+  return MI355Q_OK;
+}
+
+namespace {
+
+void set_step_knobs(const mi355q_exec_options& o) {
+  TuneKnobs k;
+  k.blocks_per_cu = o.tune_blocks_per_cu;
+  k.probe_keyed_passes = o.probe_keyed_passes;
+  k.pass_rows = o.pass_rows;
+  k.flags = o.flags;
+  k.overlap_cus = o.tune_overlap_cus;
+  set_tune_knobs(k);
+}
+
+// Whether the LDS group-by (lds_direct) or the index-partitioned family (both) is going to take the step: the derived
+// routes that would otherwise re-key it are then not asked.  (Small multi-column perfect-hash tables: the LDS group-by
+// computes the entry index from the key columns itself, no packed index column needed.)
+void members_ahead_of_routes(const mi355q_plan& plan, const mi355q_inputs& in, const mi355q_exec_options& o, const DevPlan& d,
+                             int n_cus, bool async, bool* lds_direct, bool* idx_direct) {
+  *lds_direct = *idx_direct = false;
+  if (o.force_generic || in.n_frags <= 0 || (o.kernel_variant != 0 && o.kernel_variant != 2)) return;
+  if (!(d.desc_type == MI355Q_GROUP_BY_PERFECT_HASH ||
+        (d.desc_type == MI355Q_GROUP_BY_BASELINE_HASH && d.entry_count <= 65536 && !(o.flags & MI355Q_OPT_NO_LDS_BASELINE) && !async)))
+    return;
+  int64_t tr = 0, mr = 0;
+  for (int f = 0; f < in.n_frags; ++f) {
+    tr += in.num_rows[f];
+    mr = std::max(mr, in.num_rows[f]);
+  }
+  FragView fvh{nullptr, nullptr, in.col_buffers, in.num_rows, in.n_frags, plan.n_cols, tr, mr};
+  if (o.kernel_variant == 0) *lds_direct = lds_groupby_eligible(d, fvh, n_cus);
+  // perfect-hash tables too large for LDS over plain INT keys and values: partitioned by entry index with narrow
+  // records (kernels_idx.hip) instead of packed keys + one exchange per value column (kernel_variant 2 = "the
+  // large-input members" takes it whatever the input size: tests)
+  if (!*lds_direct && !async && d.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && (tr >= kIdxPartMinRows || o.kernel_variant == 2))
+    *lds_direct = *idx_direct = idx_part_eligible(d, fvh, n_cus);
+}
+
+// ---- plan-time kernel selection (a fixed family; no JIT).  The payload probe is chosen behind this, once its payload
+// exists (join_probe_payload)
+StepKind select_family(const DevPlan& d, const FragView& fv, const mi355q_exec_options& o, int n_cus, bool bf_step, bool idx_direct,
+                       bool async) {
+  if (o.force_generic || fv.n_frags <= 0) return K_GENERIC;
+  if (bf_step) {  // a compiled filter beside the plan: only the families that take one
+    if (scan_agg_eligible(d, fv)) return K_SCAN_AGG;
+    if (o.kernel_variant == 0 && lds_groupby_eligible(d, fv, n_cus)) return K_LDS_GROUPBY;
+    return K_GENERIC;
+  }
+  if (scan_count_eligible(d, fv)) return K_SCAN_COUNT;
+  if (o.kernel_variant != 1 && scan_agg_eligible(d, fv)) return K_SCAN_AGG;
+  // (a 1-byte filter column — the row mask of a compiled filter — in front of a few-groups step: the typed LDS member reads it
+  // at 1.98 ms per 1 B rows, k_perfect_lds's 4-byte quad loads at ~3 ms: measured in round 6)
+  if (!(d.n_quals == 1 && d.quals[0].type == MI355Q_INT8 && o.kernel_variant == 0 && lds_groupby_typed_eligible(d, fv, n_cus)) &&
+      perfect_lds_eligible(d, fv))
+    return K_PERFECT_LDS;
+  // few groups: the table replicated in every workgroup's LDS (perfect-hash layouts up to 64 K entries that fit;
+  // baseline layouts whose entry guess says "small" — if the groups turn out to be too many the step is re-run)
+  if (o.kernel_variant == 0 && lds_groupby_eligible(d, fv, n_cus) &&
+      (d.desc_type == MI355Q_GROUP_BY_PERFECT_HASH || (d.entry_count <= 65536 && !(o.flags & MI355Q_OPT_NO_LDS_BASELINE) && !async)))
+    return K_LDS_GROUPBY;
+  if (idx_direct && idx_part_eligible(d, fv, n_cus)) return K_IDX_PART;
+  if (baseline_fast_eligible(d, fv)) return K_BASELINE_FAST;
+  if (!join_sum_eligible(d, fv)) return K_GENERIC;
+  // semi-join + aggregate over a large fact table: radix-partitioned probe (bitmap slices in
+  // LDS) instead of one random bitmap read per row; kernel_variant 1 / 2 force either member
+  if (o.kernel_variant != 1 && join_part_supported(d, fv, n_cus) && (o.kernel_variant == 2 || fv.total_rows >= ((int64_t)64 << 20)))
+    return K_JOIN_PART;
+  return K_JOIN_SUM;
+}
+
+// The partition scratch of the families that exchange rows: sized by the family's planner under a cap, grown in
+// ctx.scratch.  Default cap: kDefaultScratchCap, but never more than 70 % of what the device has free right now
+// (counting the scratch this context already holds), halved while the device cannot provide it (the planner then cuts
+// the input into more chunks).  A probe that finds no plan within the cap falls back to its direct member (*kind).
+int32_t size_scratch(DeviceCtx& ctx, const DevPlan& d, const FragView& fv, const JoinPayloadView& pay, const mi355q_exec_options& o,
+                     int n_cus, StepKind* kind, int64_t* scratch_bytes, int64_t* scratch_cap) {
+  if (*kind != K_BASELINE_FAST && *kind != K_JOIN_PART && *kind != K_JOIN_PROBE && *kind != K_IDX_PART) return MI355Q_OK;
+  if (*scratch_cap <= 0) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      const int64_t spare = (int64_t)((double)((int64_t)free_b + ctx.scratch.bytes) * 0.7);
+      *scratch_cap = std::max<int64_t>(std::min<int64_t>(kDefaultScratchCap, spare), (int64_t)1 << 30);
+    }
+  }
+  for (;;) {
+    *scratch_bytes = *kind == K_JOIN_PART    ? join_part_scratch_bytes(d, fv, n_cus, *scratch_cap)
+                     : *kind == K_IDX_PART   ? idx_part_scratch_bytes(d, fv, n_cus, *scratch_cap)
+                     : *kind == K_JOIN_PROBE ? join_probe_scratch_bytes(d, fv, pay, probe_cus(n_cus), *scratch_cap)
+                                             : baseline_fast_scratch_bytes(d, fv, o.kernel_variant, *scratch_cap, n_cus);
+    if (*kind == K_JOIN_PROBE && *scratch_bytes == 0) {  // no plan within this cap: the row kernel
+      *kind = join_sum_eligible(d, fv) ? K_JOIN_SUM : K_GENERIC;
+      return MI355Q_OK;
+    }
+    if (*kind == K_IDX_PART && *scratch_bytes == 0) return MI355Q_ERR_OUT_OF_GPU_MEM;  // (eligible means it plans)
+    if (*kind == K_JOIN_PART && *scratch_bytes == 0) {  // no plan within this cap: direct probe
+      *kind = K_JOIN_SUM;
+      return MI355Q_OK;
+    }
+    if (t_plan_only) return MI355Q_OK;
+    const hipError_t e = ctx.scratch.grow(*scratch_bytes);
+    if (e == hipSuccess) return MI355Q_OK;
+    (void)hipGetLastError();
+    const int64_t cur_cap = *scratch_cap > 0 ? *scratch_cap : kDefaultScratchCap;
+    if (cur_cap <= ((int64_t)1 << 30)) {
+      last_hip_error = e;
+      return MI355Q_ERR_OUT_OF_GPU_MEM;
+    }
+    *scratch_cap = cur_cap / 2;
+  }
+}
+
+// the events of a timed step, out of the context's pool: the step's pair, the launch functions' pair, their pool
+struct StepEvents {
+  hipEvent_t start = nullptr, stop = nullptr;
+  hipEvent_t* pool = nullptr;
+};
+int32_t step_events(DeviceCtx& ctx, StepEvents* ev, LaunchStats* st) {
+  constexpr int kEvPool = 128;
+  while ((int)ctx.events.size() < kEvPool + 4) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreate(&e));
+    ctx.events.push_back(e);
+  }
+  ev->start = ctx.events[0];
+  ev->stop = ctx.events[1];
+  st->k_start = ctx.events[2];
+  st->k_stop = ctx.events[3];
+  ev->pool = ctx.events.data() + 4;
+  st->ev_pool = ev->pool;
+  st->n_ev = kEvPool;
+  return MI355Q_OK;
+}
+
+// the launches of the chosen family over the uploaded table (n_frags > 0)
+hipError_t launch_family(StepKind kind, const DevPlan& d, const mi355q_qmd& q, const FragView& fv, const JoinPayloadView& pay,
+                         int64_t* buf, int32_t* d_err, const Workspace& scratch, int64_t scratch_cap, int kernel_variant, int n_cus,
+                         hipStream_t s, LaunchStats* st) {
+  switch (kind) {
+    case K_SCAN_COUNT: return launch_scan_count(d, fv, buf, n_cus, s, st);
+    case K_SCAN_AGG: return launch_scan_agg(d, fv, buf, n_cus, s, st);
+    case K_PERFECT_LDS: return launch_perfect_lds(d, fv, buf, d_err, n_cus, s, st);
+    case K_LDS_GROUPBY: return launch_lds_groupby(d, fv, buf, d_err, n_cus, s, st);
+    case K_BASELINE_FAST: return launch_baseline_fast(d, fv, buf, d_err, scratch.p, scratch.bytes, scratch_cap, kernel_variant, n_cus, s, st);
+    case K_IDX_PART: return launch_idx_partitioned(d, fv, buf, d_err, scratch.p, scratch.bytes, scratch_cap, n_cus, s, st);
+    case K_JOIN_SUM: return launch_join_sum(d, fv, buf, n_cus, s, st);
+    case K_JOIN_PART: return launch_join_partitioned(d, fv, buf, d_err, scratch.p, scratch.bytes, scratch_cap, n_cus, s, st);
+    case K_JOIN_PROBE: return launch_join_probe(d, fv, pay, buf, d_err, scratch.p, scratch.bytes, scratch_cap, probe_cus(n_cus), s, st);
+    default: break;
+  }
+  st->kernel_name = "k_generic";
+  st->n_launches = 1;
+  hipError_t e = st->k_start ? hipEventRecord(st->k_start, s) : hipSuccess;
+  if (e == hipSuccess)
+    e = launch_generic(d, q.idx_target_as_key, make_row_init(q), fv.d_cols, fv.d_num_rows, fv.n_frags, fv.max_frag_rows, buf, d_err, n_cus, s);
+  if (e == hipSuccess && st->k_stop) e = hipEventRecord(st->k_stop, s);
+  return e;
+}
+
+// what finish_step needs of a launched step, owned (the caller's arrays may be gone when mi355q_wait runs it)
+TailState* new_tail(const mi355q_plan& plan, const mi355q_inputs& in, const mi355q_qmd& q, const DevPlan& d, StepKind kind,
+                    const LaunchStats& st, mi355q_result* res, const FragTable& ft, const FragView& fv, int n_cus,
+                    const StepEvents& ev, bool trace, const DeviceCtx& ctx) {
+  TailState* tail = new (std::nothrow) TailState();
+  if (!tail) return nullptr;
+  tail->q = q;
+  tail->d = d;
+  tail->kind = kind;
+  tail->st = st;
+  tail->res = res;
+  tail->d_err = ft.d_err;
+  tail->d_cols = ft.d_cols;
+  tail->d_rows = ft.d_rows;
+  tail->h_cols.assign(in.col_buffers, in.col_buffers + (size_t)fv.n_frags * fv.n_cols);
+  tail->h_rows.assign(in.num_rows, in.num_rows + fv.n_frags);
+  tail->nf = fv.n_frags;
+  tail->nc = fv.n_cols;
+  tail->n_cus = n_cus;
+  tail->total_rows = fv.total_rows;
+  tail->max_frag_rows = fv.max_frag_rows;
+  tail->alg_bytes = algorithmic_bytes(plan, in);
+  tail->s = ft.s;
+  tail->ev_start = ev.start;
+  tail->ev_stop = ev.stop;
+  tail->ev_pool = ev.pool;
+  tail->trace = trace;
+  tail->knobs = tune_knobs();
+  tail->h_ret = (int32_t*)(ctx.h_meta + ctx.meta_bytes);
+  tail->h_ret_dev = ctx.h_ret_dev;
+  return tail;
+}
+
+// the options of the next attempt behind a retry code of finish_step
+mi355q_exec_options retry_options(int32_t code, mi355q_exec_options o) {
+  if (code == kRetryNoIdx) {
+    o.flags |= MI355Q_OPT_NO_IDX_PART;
+    return o;
+  }
+  // kRetryNoLds: small replicas did not hold the groups: the largest replica next, then eight windows of it, then another
+  // family (skipping the windows over large inputs was measured and is worse: with <= 65536 entries the families behind
+  // them are the direct global-atomic members — BH007 at 1 B rows: 29.6 ms in eight windows, 638 ms without,
+  // profiles/r04_refbench_1b_call14.jsonl)
+  o.flags |= !(o.flags & MI355Q_OPT_LDS_BASELINE_LARGE)     ? MI355Q_OPT_LDS_BASELINE_LARGE
+             : !(o.flags & MI355Q_OPT_LDS_BASELINE_WINDOWS) ? MI355Q_OPT_LDS_BASELINE_WINDOWS
+                                                            : MI355Q_OPT_NO_LDS_BASELINE;
+  return o;
+}
+
+// The upload reads the SHARED pinned block: a return that does not reach finish_step (an allocation that fails, a HIP
+// error, kNotTaken) must not leave it in flight — the next call on another stream rewrites h_meta and ctx.meta while
+// the stale copy could still land.  Disarmed where the step synchronises itself or stays in flight by
+// design (mi355q_execute_async: the next call drains it first).
+struct UploadGuard {
+  hipStream_t s;
+  bool armed;
+  ~UploadGuard() {
+    if (armed) (void)hipStreamSynchronize(s);
+  }
+};
+
+}  // namespace
+
+// The step executor: the routes in the order of DESIGN.md 3.1 (observable through mi355q_explain), then the plain step.
 // reserved != nullptr: RESERVE mode — plan the step, size and allocate the per-device workspace it would use,
 // launch nothing (mi355q_reserve_workspace); the column pointers are not looked at
 int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
@@ -549,274 +843,83 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
   if (opts) o = *opts;
   for (int i = 0; i < plan->n_quals && i < MI355Q_MAX_QUALS; ++i)
     if (MI355Q_QUAL_OR_GROUP(plan->quals[i].op) != 0) o.force_generic = 1;  // a disjunction among the quals: the row kernel
-  {
-    TuneKnobs k;
-    k.blocks_per_cu = o.tune_blocks_per_cu;
-    k.probe_keyed_passes = o.probe_keyed_passes;
-    k.pass_rows = o.pass_rows;
-    k.flags = o.flags;
-    k.overlap_cus = o.tune_overlap_cus;
-    set_tune_knobs(k);
-  }
+  set_step_knobs(o);
+  const bool async = pend != nullptr;
+  int32_t e = MI355Q_OK;  // (what the stage or route just asked answered)
+
+  // ---- steps with expressions
   bool proj_step = plan->n_targets > 0;
   for (int i = 0; i < plan->n_targets && i < MI355Q_MAX_TARGETS; ++i) proj_step = proj_step && plan->targets[i].agg == MI355Q_PROJECT;
-  // (a Projection evaluates its expressions — filters included — in the compaction kernel's registers: below)
-  if (plan->n_exprs != 0 && !pend && !step_bool_filter() && !o.force_generic && !proj_step && !(o.flags & MI355Q_OPT_NO_COMPILED_FILTER)) {
-    // A filter of comparisons with literals under AND / OR / NOT is compiled into atoms + a truth table and evaluated by
-    // the consuming kernel on the values it holds in registers (boolfilter.h): no temporary column, no second pass.
-    BoolFilterHost bfh;
-    mi355q_plan rest;
-    if (compile_bool_filter(*plan, &bfh, &rest)) {
-      const size_t mark = t_route ? t_route->size() : 0;
-      int32_t e = kNotTaken;
-      const bool fused_progs = bfh.bf.n_progs == 0 || (bfh.bf.all_lean && bfh.bf.all_i32 && bfh.bf.n_progs <= kLdsFusedProgs &&
-                                                       !(o.flags & MI355Q_OPT_FILTER_PREPASS));
-      if (fused_progs) {
-        DeviceGuard gb(in->device_id);
-        DeviceCtx& cb = ctx_of(in->device_id);
-        std::lock_guard<std::recursive_mutex> lb(cb.mu);
-        bool have = true;
-        if (!t_plan_only) {
-          if (!cb.bf_table) have = gb.ok && hipMalloc(&cb.bf_table, sizeof(BoolFilter)) == hipSuccess;
-          // (a synchronous copy out of this frame: atoms + truth table, 1.2 KB)
-          have = have && hipMemcpy(cb.bf_table, &bfh.bf, sizeof(BoolFilter), hipMemcpyHostToDevice) == hipSuccess;
-        }
-        if (have) {
-          struct BfScope {
-            BfScope(const BoolFilter* b, const BoolFilter* d) { set_step_bool_filter(b, d); }
-            ~BfScope() { set_step_bool_filter(nullptr, nullptr); }
-          } scope(&bfh.bf, (const BoolFilter*)cb.bf_table);
-          route_note("filter compiled (atoms + truth table)");
-          e = execute_impl(&rest, in, &o, out, report, nullptr, reserved);
-        } else {
-          (void)hipGetLastError();
-        }
-      }
-      if (e == kNotTaken && bfh.bf.n_progs != 0) {  // program atoms no family evaluates itself: the row-mask pre-pass, then `mask = 1`
-        if (t_route) t_route->resize(mark);
-        *out = nullptr;
-        route_note("filter compiled (atoms + programs + truth table)");
-        e = execute_masked(plan, rest, bfh, in, o, out, report, reserved);
-      }
-      if (e != kNotTaken) {
-        if (e == MI355Q_OK && report && !reserved) report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-        return e;
-      }
-      if (t_route) t_route->resize(mark);
-      *out = nullptr;
-    }
-  }
-  if (plan->n_exprs != 0 && proj_step && !pend && !step_bool_filter() && !o.force_generic && !(o.flags & MI355Q_OPT_NO_COMPILED_FILTER)) {
-    // a Projection whose expressions all belong to the FILTER (`SELECT a, b FROM t WHERE x + y > 100`): the filter is compiled,
-    // the row-mask pre-pass evaluates it, the Projection runs on `mask = 1` — in its fast member where the targets allow —
-    // instead of evaluating the quals' expressions row by row in the general member.  With a LIMIT only where the filter
-    // cannot raise: the pre-pass looks at every row, the reference's loop stops at the limit.
-    BoolFilterHost bfh;
-    mi355q_plan rest;
-    if (compile_bool_filter(*plan, &bfh, &rest) && (!bfh.bf.any_raise || plan->scan_limit == 0)) {
-      const size_t mark = t_route ? t_route->size() : 0;
-      route_note("filter compiled (atoms + programs + truth table)");
-      const int32_t e = execute_masked(plan, rest, bfh, in, o, out, report, reserved);
-      if (e != kNotTaken) return e;
-      if (t_route) t_route->resize(mark);
-      *out = nullptr;
-    }
-  }
   if (plan->n_exprs != 0) {
-    {  // a Projection evaluates its expressions in the compaction kernel's registers: no k_project pass
-      if (proj_step) return execute_projection(plan, in, o, out, report, reserved);
-    }
-    if (!pend) {
-      const size_t mark = t_route ? t_route->size() : 0;
-      int32_t e = execute_shifted_args(plan, in, o, out, report, reserved);
+    if (!async && !step_bool_filter() && !o.force_generic && !(o.flags & MI355Q_OPT_NO_COMPILED_FILTER)) {
+      // (a Projection evaluates its expressions — filters included — in the compaction kernel's registers, unless they all
+      // belong to its filter)
+      e = proj_step ? execute_projection_filter(plan, in, o, out, report, reserved)
+                    : execute_compiled_filter(plan, in, o, out, report, reserved);
       if (e != kNotTaken) return e;
-      if (t_route) t_route->resize(mark);
-      e = execute_cast_key(plan, in, o, out, report, reserved);
-      if (e != kNotTaken) return e;
-      if (t_route) t_route->resize(mark);
     }
+    if (proj_step) return execute_projection(plan, in, o, out, report, reserved);  // no k_project pass
+    if (!async && (e = try_route(out, [&] { return execute_shifted_args(plan, in, o, out, report, reserved); })) != kNotTaken) return e;
+    if (!async && (e = try_route(out, [&] { return execute_cast_key(plan, in, o, out, report, reserved); })) != kNotTaken) return e;
     if (reserved) {  // the step proper runs on the lowered plan: reserve for that
       route_note("k_project");
       mi355q_plan lp;
-      if (int32_t e = lower_exprs(*plan, &lp, nullptr, true)) return e;
+      if ((e = lower_exprs(*plan, &lp, nullptr, true))) return e;
       return execute_impl(&lp, in, &o, out, report, nullptr, reserved);
     }
     return execute_projected(plan, in, o, out, report);
   }
 
+  // ---- the plan as the device sees it
   Trace tr((o.flags & MI355Q_OPT_TRACE) != 0);
   mi355q_qmd q;
-  if (int32_t e = qmd_init(*plan, &q)) return e;
+  if ((e = qmd_init(*plan, &q))) return e;
   if (q.desc_type == MI355Q_PROJECTION) return execute_projection(plan, in, o, out, report, reserved);
   DevPlan d;
-  if (int32_t e = build_dev_plan(*plan, q, &d)) return e;
-  if (int32_t e = attach_join(*plan, in, &d)) return e;
+  if ((e = build_dev_plan(*plan, q, &d))) return e;
+  if ((e = attach_join(*plan, in, &d))) return e;
   // a compiled filter travels beside the plan (its quals are gone): only the families that take one may run the step —
   // no derived plans, no row kernel; kNotTaken sends the caller back to the projection pass
   d.bf_active = step_bool_filter() != nullptr;
   const bool bf_step = d.bf_active != 0;
-
   DeviceGuard g(in->device_id);
   if (!g.ok) return MI355Q_ERR_HIP;
   const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
 
-  if (q.output_columnar) {
-    // Columnar output: the step runs on the row-wise form of the same decisions (same entry
-    // count, 8-byte key components, same hash, same slots) into a library-owned table, and the
-    // finished table is moved column by column into the caller-visible buffer.
-    mi355q_plan pr = *plan;
-    pr.output_columnar_hint = MI355Q_OUTPUT_ROWWISE_COLUMNAR_DECISIONS;
-    mi355q_exec_options orw = o;
-    orw.out_buffer = nullptr;
-    if (reserved) {
-      route_note("row-wise twin + k_rows_to_columns");
-      return execute_impl(&pr, in, &orw, out, report, nullptr, reserved);
-    }
-    RowTwin t;
-    if (int32_t e = mi355q_execute(&pr, in, &orw, &t.tw, report)) return e;
-    const mi355q_qmd& qr = t.tw->qmd;
-    if (qr.entry_count != q.entry_count || qr.row_size != q.row_size || qr.key_bytes != q.key_bytes ||
-        qr.slot_count != q.slot_count || qr.slot_width != q.slot_width || qr.output_columnar)
-      return MI355Q_ERR_UNSUPPORTED;
-    mi355q_result* rc = nullptr;
-    if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &rc)) return e;
-    if (int32_t e = store_row_twin(t, rc, (hipStream_t)o.stream)) {
-      mi355q_result_free(rc);
-      return e;
-    }
-    *out = rc;
-    return MI355Q_OK;
-  }
+  // ---- the layout twins
+  if (q.output_columnar) return execute_columnar_twin(plan, in, o, q, out, report, reserved);
+  if (q.slot_width == 4) return execute_wide_slot_twin(plan, in, o, q, out, report, reserved);
 
-  if (q.slot_width == 4) {
-    // Compact layout (4-byte slots): the step runs on the 8-byte layout of the same plan — same
-    // entry count, same key bytes, same hash — and the finished table is narrowed row by row.
-    int64_t rows = 0;
-    for (int f = 0; f < in->n_frags; ++f) rows += in->num_rows[f];
-    if (rows > (int64_t)UINT32_MAX) return MI355Q_ERR_INVALID_PLAN;  // a 32-bit COUNT would wrap
-    mi355q_plan p8 = *plan;
-    p8.bigint_count = 1;  // pick_target_compact_width: g_bigint_count -> 8-byte slots
-    mi355q_qmd q8;
-    if (int32_t e = qmd_init(p8, &q8)) return e;
-    if (q8.slot_width != 8 || q8.entry_count != q.entry_count || q8.key_bytes != q.key_bytes ||
-        q8.slot_count != q.slot_count)
-      return MI355Q_ERR_UNSUPPORTED;
-    if (reserved) {
-      route_note("8-byte-slot twin + k_narrow_slots");
-      return execute_impl(&p8, in, &o, out, report, nullptr, reserved);
-    }
-    DeviceCtx& ctx = ctx_of(in->device_id);
-    std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-    const int64_t need = q8.entry_count * (int64_t)q8.row_size;
-    if (ctx.wide_bytes < need) {
-      if (ctx.wide) (void)hipFree(ctx.wide);
-      ctx.wide = nullptr;
-      ctx.wide_bytes = 0;
-      hipError_t he = hipMalloc(&ctx.wide, (size_t)need);
-      if (he != hipSuccess) {
-        last_hip_error = he;
-        return MI355Q_ERR_OUT_OF_GPU_MEM;
-      }
-      ctx.wide_bytes = need;
-    }
-    hipStream_t s4 = (hipStream_t)o.stream;
-    if (!s4) {
-      if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-      s4 = ctx.stream;
-    }
-    mi355q_exec_options o8 = o;
-    o8.stream = s4;
-    o8.out_buffer = ctx.wide;
-    mi355q_result* r8 = nullptr;
-    if (int32_t e = mi355q_execute(&p8, in, &o8, &r8, report)) return e;
-    mi355q_result_free(r8);
-    mi355q_result* res4 = nullptr;
-    if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res4)) return e;
-    hipError_t he = launch_narrow_slots((const int64_t*)ctx.wide, q8.row_size / 8, q.key_bytes / 8, q.slot_count,
-                                        q.row_size / 8, q.entry_count, res4->buf, s4);
-    if (he == hipSuccess) he = hipStreamSynchronize(s4);
-    if (he != hipSuccess) {
-      last_hip_error = he;
-      mi355q_result_free(res4);
-      return MI355Q_ERR_HIP;
-    }
-    *out = res4;
-    return MI355Q_OK;
-  }
-
-  // (small multi-column perfect-hash tables: the LDS group-by computes the entry index from the key columns itself,
-  // no packed index column needed)
+  // ---- the derived-plan routes, each asked unless a member that needs none of them is going to take the step
   bool lds_direct = false, idx_direct = false;
-  if (!o.force_generic && in->n_frags > 0 && (o.kernel_variant == 0 || o.kernel_variant == 2) &&
-      (d.desc_type == MI355Q_GROUP_BY_PERFECT_HASH ||
-       (d.desc_type == MI355Q_GROUP_BY_BASELINE_HASH && d.entry_count <= 65536 && !(o.flags & MI355Q_OPT_NO_LDS_BASELINE) && !pend))) {
-    int64_t tr = 0, mr = 0;
-    for (int f = 0; f < in->n_frags; ++f) {
-      tr += in->num_rows[f];
-      mr = std::max(mr, in->num_rows[f]);
-    }
-    FragView fvh{nullptr, nullptr, in->col_buffers, in->num_rows, in->n_frags, plan->n_cols, tr, mr};
-    if (o.kernel_variant == 0) lds_direct = lds_groupby_eligible(d, fvh, n_cus);
-    // perfect-hash tables too large for LDS over plain INT keys and values: partitioned by entry index with narrow
-    // records (kernels_idx.hip) instead of packed keys + one exchange per value column (kernel_variant 2 = "the
-    // large-input members" takes it whatever the input size: tests)
-    if (!lds_direct && !pend && d.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && (tr >= kIdxPartMinRows || o.kernel_variant == 2))
-      lds_direct = idx_direct = idx_part_eligible(d, fvh, n_cus);
-  }
+  members_ahead_of_routes(*plan, *in, o, d, n_cus, async, &lds_direct, &idx_direct);
   if (bf_step && in->n_frags <= 0) return kNotTaken;
   if (bf_step && q.desc_type != MI355Q_NON_GROUPED_AGGREGATE && (!lds_direct || idx_direct)) return kNotTaken;
-  if (!pend && plan->join_outer_col >= 0 && !bf_step) {
-    const size_t mark = t_route ? t_route->size() : 0;
-    const int32_t e = execute_dense_join_as_filter(plan, in, o, out, report, reserved);
-    if (e != kNotTaken) return e;
-    if (t_route) t_route->resize(mark);
-    *out = nullptr;
-  }
-  if (!o.force_generic && in->n_frags > 0 && !pend && plan->join_outer_col >= 0 && !bf_step) {
-    const size_t mark = t_route ? t_route->size() : 0;
-    const int32_t e = execute_join_gather(plan, in, o, q, d, n_cus, out, report, reserved);
-    if (e != kNotTaken) return e;
-    if (t_route) t_route->resize(mark);
-    *out = nullptr;
-  }
-  if (!o.force_generic && in->n_frags > 0 && !lds_direct && !pend) {
-    const size_t mark = t_route ? t_route->size() : 0;
-    const int32_t e = execute_perfect_twin(plan, in, o, q, n_cus, out, report, reserved);
-    if (e != kNotTaken) return e;
-    if (t_route) t_route->resize(mark);
-    *out = nullptr;
-  }
-  if (!o.force_generic && in->n_frags > 0 && !pend && !reserved) {
-    // (before the LDS attempt on a small baseline table too: BH007's 10 K lattice points are a typed LDS member's work)
-    const int32_t e = execute_affine_twin(plan, in, o, q, n_cus, out, report, reserved);
-    if (e != kNotTaken) return e;
-    *out = nullptr;
-  }
-  if (!o.force_generic && in->n_frags > 0 && !lds_direct) {
-    const size_t mark = t_route ? t_route->size() : 0;
-    const int32_t e = execute_packed_multi(plan, in, o, q, d, n_cus, out, report, reserved);
-    if (e != kNotTaken) return e;
-    if (t_route) t_route->resize(mark);
-    *out = nullptr;
-  }
+  const bool fast = !o.force_generic && in->n_frags > 0;
+  const bool join = plan->join_outer_col >= 0 && !bf_step;
+  if (!async && join && (e = try_route(out, [&] { return execute_dense_join_as_filter(plan, in, o, out, report, reserved); })) != kNotTaken)
+    return e;
+  if (fast && !async && join && (e = try_route(out, [&] { return execute_join_gather(plan, in, o, q, d, n_cus, out, report, reserved); })) != kNotTaken)
+    return e;
+  if (fast && !lds_direct && !async &&
+      (e = try_route(out, [&] { return execute_perfect_twin(plan, in, o, q, n_cus, out, report, reserved); })) != kNotTaken)
+    return e;
+  // (before the LDS attempt on a small baseline table too: BH007's 10 K lattice points are a typed LDS member's work)
+  if (fast && !async && !reserved &&
+      (e = try_route(out, [&] { return execute_affine_twin(plan, in, o, q, n_cus, out, report, reserved); })) != kNotTaken)
+    return e;
+  if (fast && !lds_direct && (e = try_route(out, [&] { return execute_packed_multi(plan, in, o, q, d, n_cus, out, report, reserved); })) != kNotTaken)
+    return e;
+  // several value columns over a large input, and the LDS group-by is not going to take the step (table too large,
+  // a forced variant, or its attempts already failed): one run per value column, zipped
+  if (fast && !lds_direct && o.kernel_variant != 1 && d.n_group >= 1 &&
+      (e = try_route(out, [&] { return execute_multi_value(plan, in, o, q, d, out, report, reserved); }, /*unsupported_too=*/true)) != kNotTaken)
+    return e;
 
-  if (!o.force_generic && in->n_frags > 0 && !lds_direct && o.kernel_variant != 1 && d.n_group >= 1) {
-    // several value columns over a large input, and the LDS group-by is not going to take the step (table too large,
-    // a forced variant, or its attempts already failed): one run per value column, zipped
-    const size_t mark = t_route ? t_route->size() : 0;
-    const int32_t e = execute_multi_value(plan, in, o, q, d, out, report, reserved);
-    if (e != kNotTaken && e != MI355Q_ERR_UNSUPPORTED) return e;
-    if (t_route) t_route->resize(mark);
-    *out = nullptr;
-  }
-
-  hipStream_t s = (hipStream_t)o.stream;  // caller's, or the device context's own (below)
-
+  // ---- the plain step: result, fragment table, family, payload, scratch
   mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
+  if ((e = result_create_impl(&q, in->device_id, o.out_buffer, &res))) return e;
   ResultPtr owned(res);
-
-  // device copies of the fragment tables + error word, one allocation
   const int nf = in->n_frags, nc = plan->n_cols;
   int64_t total_rows = 0, max_frag_rows = 0;
   for (int f = 0; f < nf; ++f) {
@@ -824,404 +927,61 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
     total_rows += in->num_rows[f];
     max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
   }
-  const size_t ptr_bytes = sizeof(void*) * (size_t)std::max(1, nf * nc);
-  const size_t rows_bytes = sizeof(int64_t) * (size_t)std::max(1, nf);
-  const size_t meta_bytes = ptr_bytes + rows_bytes + 64;
   DeviceCtx& ctx = ctx_of(in->device_id);
   std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  if (ctx.meta_bytes < meta_bytes) {
-    if (ctx.meta) (void)hipFree(ctx.meta);
-    ctx.meta = nullptr;
-    ctx.meta_bytes = 0;
-    if (ctx.h_meta) (void)hipHostFree(ctx.h_meta);
-    ctx.h_meta = nullptr;
-    ctx.h_ret_dev = nullptr;
-    ctx.meta_shadow.clear();
-    HIP_TRY(hipMalloc(&ctx.meta, meta_bytes * 2));
-    HIP_TRY(hipHostMalloc((void**)&ctx.h_meta, meta_bytes * 2 + 64, hipHostMallocDefault));
-    ctx.meta_bytes = meta_bytes * 2;
-  }
-  if (!ctx.h_ret_dev && ctx.h_meta) {
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, ctx.h_meta + ctx.meta_bytes, 0) == hipSuccess) ctx.h_ret_dev = (int32_t*)dp;
-    else (void)hipGetLastError();
-  }
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  char* mp = (char*)ctx.meta;
-  const int8_t* const* d_cols = (const int8_t* const*)mp;
-  const int64_t* d_rows = (const int64_t*)(mp + ptr_bytes);
-  int32_t* d_err = (int32_t*)(mp + ptr_bytes + rows_bytes);
-  {
-    // one copy out of pinned memory: column table | row counts | zeroed error words (the synchronous step of a 60 us scan
-    // used to spend ~90 us on a memset and two copies out of pageable memory, each staged by the driver; VERDICT r03 weak #6)
-    char* hm = ctx.h_meta;
-    const size_t tab_bytes = ptr_bytes + rows_bytes;
-    // the same table as the last upload, its error words untouched since: nothing to send
-    bool same = !reserved && nf > 0 && ctx.meta_err_clean && ctx.meta_shadow.size() == tab_bytes &&
-                !std::memcmp(ctx.meta_shadow.data(), in->col_buffers, sizeof(void*) * (size_t)(nf * nc)) &&
-                !std::memcmp(ctx.meta_shadow.data() + ptr_bytes, in->num_rows, sizeof(int64_t) * (size_t)nf);
-    if (!same && !reserved) {  // (reserve / explain launch nothing: no upload to leave in flight)
-      if (nf > 0) {
-        std::memcpy(hm, in->col_buffers, sizeof(void*) * (size_t)(nf * nc));
-        std::memcpy(hm + ptr_bytes, in->num_rows, sizeof(int64_t) * (size_t)nf);
-      }
-      std::memset(hm + ptr_bytes + rows_bytes, 0, 64);
-      const size_t lo = nf > 0 ? 0 : ptr_bytes + rows_bytes;
-      HIP_TRY(hipMemcpyAsync(mp + lo, hm + lo, ptr_bytes + rows_bytes + 64 - lo, hipMemcpyHostToDevice, s));
-      if (nf > 0) ctx.meta_shadow.assign(hm, hm + tab_bytes);
-      else ctx.meta_shadow.clear();
-    }
-    ctx.meta_err_clean = false;  // (until this step's words have been read back as zeros: below)
-  }
-  // The upload reads the SHARED pinned block: a return that does not reach finish_step (an allocation that fails, a HIP
-  // error, kNotTaken) must not leave it in flight — the next call on another stream rewrites h_meta and ctx.meta while
-  // the stale copy could still land.  Disarmed where the step synchronises itself or stays in flight by
-  // design (mi355q_execute_async: the next call drains it first).
-  struct UploadGuard {
-    hipStream_t s;
-    bool armed;
-    ~UploadGuard() {
-      if (armed) (void)hipStreamSynchronize(s);
-    }
-  } upload_guard{s, !reserved};
-
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  FragTable ft;  // (reserve / explain launch nothing: no upload to leave in flight)
+  if ((e = upload_frag_table(ctx, *in, nc, o.stream, reserved ? FragUpload::kNone : FragUpload::kSkipUnchanged, &ft))) return e;
+  hipStream_t s = ft.s;
+  UploadGuard upload_guard{s, !reserved};
+  StepEvents ev;
   LaunchStats st;
-  constexpr int kEvPool = 128;
-  hipEvent_t* ev_pool = nullptr;
-  if (report) {
-    while ((int)ctx.events.size() < kEvPool + 4) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      ctx.events.push_back(e);
-    }
-    ev_start = ctx.events[0];
-    ev_stop = ctx.events[1];
-    st.k_start = ctx.events[2];
-    st.k_stop = ctx.events[3];
-    ev_pool = ctx.events.data() + 4;
-    st.ev_pool = ev_pool;
-    st.n_ev = kEvPool;
-  }
+  if (report && (e = step_events(ctx, &ev, &st))) return e;
+  FragView fv{ft.d_cols, ft.d_rows, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
 
-  FragView fv{d_cols, d_rows, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
-
-  // ---- plan-time kernel selection (a fixed family; no JIT)
-  StepKind kind = K_GENERIC;
+  StepKind kind = select_family(d, fv, o, n_cus, bf_step, idx_direct, async);
+  if (kind == K_GENERIC && !bf_step && fast && !async && plan->n_quals >= 2 && d.join_col < 0 &&
+      (total_rows >= ((int64_t)1 << 20) || o.kernel_variant == 2) && !(o.flags & MI355Q_OPT_NO_COMPILED_FILTER) &&
+      (e = execute_compiled_quals(plan, in, o, out, report, reserved)) != kNotTaken)
+    return e;
+  // joins that read the inner side / one-to-many tables / LEFT joins over a large outer table: the payload probe.  The
+  // semi-join shapes keep their 1-bit-per-key member above.
   JoinPayloadView pay{};
-  if (bf_step) {
-    if (!o.force_generic && nf > 0 && scan_agg_eligible(d, fv)) kind = K_SCAN_AGG;
-    else if (!o.force_generic && nf > 0 && o.kernel_variant == 0 && lds_groupby_eligible(d, fv, n_cus)) kind = K_LDS_GROUPBY;
-  } else if (!o.force_generic && nf > 0) {
-    if (scan_count_eligible(d, fv)) kind = K_SCAN_COUNT;
-    else if (o.kernel_variant != 1 && scan_agg_eligible(d, fv)) kind = K_SCAN_AGG;
-    // (a 1-byte filter column — the row mask of a compiled filter — in front of a few-groups step: the typed LDS member reads it
-    // at 1.98 ms per 1 B rows, k_perfect_lds's 4-byte quad loads at ~3 ms: measured in round 6)
-    else if (!(d.n_quals == 1 && d.quals[0].type == MI355Q_INT8 && o.kernel_variant == 0 && lds_groupby_typed_eligible(d, fv, n_cus)) &&
-             perfect_lds_eligible(d, fv))
-      kind = K_PERFECT_LDS;
-    // few groups: the table replicated in every workgroup's LDS (perfect-hash layouts up to 64 K entries that fit;
-    // baseline layouts whose entry guess says "small" — if the groups turn out to be too many the step is re-run)
-    else if (o.kernel_variant == 0 && lds_groupby_eligible(d, fv, n_cus) &&
-             (d.desc_type == MI355Q_GROUP_BY_PERFECT_HASH ||
-              (d.entry_count <= 65536 && !(o.flags & MI355Q_OPT_NO_LDS_BASELINE) && !pend)))
-      kind = K_LDS_GROUPBY;
-    else if (idx_direct && idx_part_eligible(d, fv, n_cus)) kind = K_IDX_PART;
-    else if (baseline_fast_eligible(d, fv)) kind = K_BASELINE_FAST;
-    else if (join_sum_eligible(d, fv)) kind = K_JOIN_SUM;
-    // semi-join + aggregate over a large fact table: radix-partitioned probe (bitmap slices in
-    // LDS) instead of one random bitmap read per row; kernel_variant 1 / 2 force either member
-    if (kind == K_JOIN_SUM && o.kernel_variant != 1 && join_part_supported(d, fv, n_cus) &&
-        (o.kernel_variant == 2 || total_rows >= ((int64_t)64 << 20)))
-      kind = K_JOIN_PART;
-  }
-
-  // SEVERAL plain quals in front of a family that filters on one column (the partitioned GROUP BY, the perfect-hash LDS
-  // member, the index-partitioned family takes none): instead of the row kernel, the quals become the range atoms of a
-  // compiled filter, the row-mask pre-pass evaluates them (k_filter_mask: one byte per row) and the step runs on
-  // `mask = 1` — measured in round 6: `a < K AND b > L` over 10 M INT64 groups went to k_generic at 55 ms per 1 B rows
-  if (kind == K_GENERIC && !bf_step && !o.force_generic && nf > 0 && !pend && plan->n_exprs == 0 && plan->n_quals >= 2 &&
-      d.join_col < 0 && q.desc_type != MI355Q_PROJECTION && (total_rows >= ((int64_t)1 << 20) || o.kernel_variant == 2) &&
-      !(o.flags & MI355Q_OPT_NO_COMPILED_FILTER)) {
-    BoolFilterHost bfh;
-    mi355q_plan rest;
-    if (compile_bool_filter(*plan, &bfh, &rest)) {
-      const size_t mark = t_route ? t_route->size() : 0;
-      route_note("quals compiled (range atoms + truth table)");
-      const int32_t e = execute_masked(plan, rest, bfh, in, o, out, report, reserved);
-      if (e != kNotTaken) return e;
-      if (t_route) t_route->resize(mark);
-      *out = nullptr;
-    }
-  }
-
-  // joins that read the inner side / one-to-many tables / LEFT joins over a large outer table: the
-  // payload probe (per-key aggregated payload of the perfect table in LDS).  The semi-join shapes
-  // keep their 1-bit-per-key member above.
-  // The L2 members of that probe map workgroup b to XCD b % 8 and group b / 8 and walk the runs with stride
-  // gridDim / 8: they are planned and launched with a multiple of 8 workgroups, or not at all (found by the host
-  // simulation, which first ran them on "4 CUs": gridDim / 8 = 0 never advances — on the device a `tune_cus` below 8
-  // would have hung the GPU, and one that is not a multiple of 8 would have read some runs twice).
-  const int n_cus_probe = n_cus >= 8 ? (n_cus & ~7) : 0;
-  if (!o.force_generic && nf > 0 && kind != K_JOIN_PART && o.kernel_variant != 1 && plan->join_table && !reserved &&
-      d.join_col >= 0 && (o.kernel_variant == 3 || total_rows >= ((int64_t)16 << 20))) {
-    int wcol = -1, l2 = 0;
-    if (n_cus_probe && join_probe_wants(d, fv, n_cus_probe, &wcol, &l2)) {
-      mi355q_join_table* jt = const_cast<mi355q_join_table*>(plan->join_table);
-      const void* inner = wcol >= 0 ? (const void*)d.inner_cols[wcol] : nullptr;
-      std::lock_guard<std::mutex> pl(jt->pay_mu);
-      const int64_t entries = jt->entry_count;
-      bool ok = !(jt->pay_refused && jt->pay_refused_col == inner && jt->pay_refused_rows == total_rows);
-      // a cached payload is only as good as the column it was derived from: same address AND same generation
-      const bool have = l2 ? (jt->pay16_built && (!inner || (jt->pay16_col == inner && jt->pay16_version == in->inner_version)))
-                           : (jt->pay_col_built && (!inner || (jt->pay_col == inner && jt->pay_version == in->inner_version)));
-      if (ok && !have) {
-        // (re)build for this inner column, in the layout the chosen mode reads
-        hipEvent_t b0 = nullptr, b1 = nullptr;
-        (void)hipEventCreate(&b0);
-        (void)hipEventCreate(&b1);
-        DevWord flags;
-        ok = hipMalloc(&flags.p, 64) == hipSuccess;
-        if (l2) {
-          if (ok && !jt->pay16) ok = hipMalloc(&jt->pay16, (size_t)entries * 16) == hipSuccess;
-          // one-to-one tables: the 8-byte payload — interleaved with the slot's key for a keyed table
-          if (ok && (jt->hash_type == 0 || jt->hash_type == 1) && !jt->pay8)
-            ok = hipMalloc((void**)&jt->pay8, (size_t)entries * (l2 == 2 ? 16 : 8)) == hipSuccess;
-          // (one spare key behind the end: the keyed probe reads the keys two at a time)
-          if (ok && l2 == 2 && !jt->pay_kkeys) ok = hipMalloc((void**)&jt->pay_kkeys, (size_t)entries * 8 + 16) == hipSuccess;
-        } else {
-          if (ok && !jt->pay_cnt) ok = hipMalloc((void**)&jt->pay_cnt, (size_t)entries * 4) == hipSuccess;
-          if (ok && inner && !jt->pay_wsum) ok = hipMalloc((void**)&jt->pay_wsum, (size_t)entries * 8) == hipSuccess;
-          if (ok && inner && !jt->pay_wnn) ok = hipMalloc((void**)&jt->pay_wnn, (size_t)entries * 4) == hipSuccess;
-        }
-        if (ok) {
-          (void)hipMemsetAsync(flags.p, 0, 64, s);
-          if (b0) (void)hipEventRecord(b0, s);
-          ok = (l2 == 2 ? launch_join_payload_keyed_build(jt->buf, jt->hash_type, entries, inner, jt->pay_kkeys, jt->pay16,
-                                                          jt->pay8, (int32_t*)flags.p, n_cus, s)
-                        : launch_join_payload_build(jt->buf, jt->hash_type, entries, inner, jt->pay_cnt, jt->pay_wsum,
-                                                    jt->pay_wnn, l2 ? jt->pay16 : nullptr, l2 ? jt->pay8 : nullptr,
-                                                    (int32_t*)flags.p, n_cus, s)) == hipSuccess;
-          if (b1) (void)hipEventRecord(b1, s);
-          int32_t h_flags = 0;
-          ok = ok && hipMemcpyAsync(&h_flags, flags.p, 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
-               hipStreamSynchronize(s) == hipSuccess;
-          if (ok) {
-            if (l2) {
-              jt->pay16_built = true;
-              jt->pay16_col = inner;
-              jt->pay16_version = in->inner_version;
-              jt->pay16_has_nulls = h_flags & 1;
-            } else {
-              jt->pay_col_built = true;
-              jt->pay_col = inner;
-              jt->pay_version = in->inner_version;
-              jt->pay_has_nulls = h_flags & 1;
-            }
-            if (b0 && b1) (void)hipEventElapsedTime(&jt->pay_build_ms, b0, b1);
-          }
-        }
-        if (b0) (void)hipEventDestroy(b0);
-        if (b1) (void)hipEventDestroy(b1);
-        if (!ok) (void)hipGetLastError();
-      }
-      if (ok) {
-        pay.cnt_k = l2 ? nullptr : jt->pay_cnt;
-        pay.wsum_k = (!l2 && inner) ? jt->pay_wsum : nullptr;
-        pay.wnn_k = (!l2 && inner) ? jt->pay_wnn : nullptr;
-        pay.pay16 = l2 ? jt->pay16 : nullptr;
-        pay.pay8 = l2 ? jt->pay8 : nullptr;
-        pay.kkeys = l2 == 2 ? jt->pay_kkeys : nullptr;
-        pay.inner_col = inner;
-        pay.entries = entries;
-        pay.has_nulls = l2 ? jt->pay16_has_nulls : jt->pay_has_nulls;
-        if (join_probe_supported(d, fv, pay, n_cus_probe)) {
-          kind = K_JOIN_PROBE;
-        } else {
-          // the probe plan does not take this payload after all: entries x 16 B of device memory are not kept for a
-          // member that will not run (the step falls back to k_join_sum / the row kernel below)
-          auto drop = [](auto*& ptr) {
-            if (ptr) (void)hipFree((void*)ptr);
-            ptr = nullptr;
-          };
-          if (l2) {
-            drop(jt->pay16);
-            drop(jt->pay8);
-            drop(jt->pay_kkeys);
-            jt->pay16_built = false;
-            jt->pay16_col = nullptr;
-          } else {
-            drop(jt->pay_cnt);
-            drop(jt->pay_wsum);
-            drop(jt->pay_wnn);
-            jt->pay_col_built = false;
-            jt->pay_col = nullptr;
-          }
-          pay = JoinPayloadView{};
-          jt->pay_refused = true;
-          jt->pay_refused_col = inner;
-          jt->pay_refused_rows = total_rows;
-        }
-      }
-    }
-  }
-
+  if (fast && kind != K_JOIN_PART && o.kernel_variant != 1 && plan->join_table && !reserved && d.join_col >= 0 &&
+      (o.kernel_variant == 3 || total_rows >= ((int64_t)16 << 20)) &&
+      join_probe_payload(const_cast<mi355q_join_table*>(plan->join_table), d, fv, in->inner_version, s, n_cus, &pay))
+    kind = K_JOIN_PROBE;
   if (bf_step && kind != K_LDS_GROUPBY && kind != K_SCAN_AGG) return kNotTaken;
   tr.mark("setup done");
-  int64_t scratch_bytes = 0;
-  int64_t scratch_cap = o.scratch_bytes;
-  if (kind == K_BASELINE_FAST || kind == K_JOIN_PART || kind == K_JOIN_PROBE || kind == K_IDX_PART) {
-    // default cap: kDefaultScratchCap, but never more than 70 % of what the device has free right now
-    // (counting the scratch this context already holds), halved while the device cannot provide it
-    // (the planner then cuts the input into more chunks)
-    if (scratch_cap <= 0) {
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const int64_t spare = (int64_t)((double)((int64_t)free_b + ctx.scratch_bytes) * 0.7);
-        scratch_cap = std::max<int64_t>(std::min<int64_t>(kDefaultScratchCap, spare), (int64_t)1 << 30);
-      }
-    }
-    for (;;) {
-      scratch_bytes = kind == K_JOIN_PART    ? join_part_scratch_bytes(d, fv, n_cus, scratch_cap)
-                      : kind == K_IDX_PART   ? idx_part_scratch_bytes(d, fv, n_cus, scratch_cap)
-                      : kind == K_JOIN_PROBE ? join_probe_scratch_bytes(d, fv, pay, n_cus_probe, scratch_cap)
-                                             : baseline_fast_scratch_bytes(d, fv, o.kernel_variant, scratch_cap, n_cus);
-      if (kind == K_JOIN_PROBE && scratch_bytes == 0) {  // no plan within this cap: the row kernel
-        kind = join_sum_eligible(d, fv) ? K_JOIN_SUM : K_GENERIC;
-        break;
-      }
-      if (kind == K_IDX_PART && scratch_bytes == 0) return MI355Q_ERR_OUT_OF_GPU_MEM;  // (eligible means it plans)
-      if (kind == K_JOIN_PART && scratch_bytes == 0) {  // no plan within this cap: direct probe
-        kind = K_JOIN_SUM;
-        break;
-      }
-      if (scratch_bytes <= ctx.scratch_bytes || t_plan_only) break;
-      if (ctx.scratch) (void)hipFree(ctx.scratch);
-      ctx.scratch = nullptr;
-      ctx.scratch_bytes = 0;
-      hipError_t e = hipMalloc(&ctx.scratch, (size_t)scratch_bytes);
-      if (e == hipSuccess) {
-        ctx.scratch_bytes = scratch_bytes;
-        break;
-      }
-      (void)hipGetLastError();
-      const int64_t cur_cap = scratch_cap > 0 ? scratch_cap : kDefaultScratchCap;
-      if (cur_cap <= ((int64_t)1 << 30)) {
-        last_hip_error = e;
-        return MI355Q_ERR_OUT_OF_GPU_MEM;
-      }
-      scratch_cap = cur_cap / 2;
-    }
-  }
-
+  int64_t scratch_bytes = 0, scratch_cap = o.scratch_bytes;
+  if ((e = size_scratch(ctx, d, fv, pay, o, n_cus, &kind, &scratch_bytes, &scratch_cap))) return e;
   tr.mark("scratch allocated");
   if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched
-    if (t_route) {
-      char note[96];
-      const char* name = kind == K_SCAN_COUNT ? "k_scan_count" : kind == K_SCAN_AGG ? "k_scan_agg"
-                         : kind == K_PERFECT_LDS ? "k_perfect_lds" : kind == K_LDS_GROUPBY ? "k_groupby_lds"
-                         : kind == K_JOIN_SUM ? "k_join_sum" : kind == K_JOIN_PART ? "k_part_scatter + k_part_join"
-                         : kind == K_JOIN_PROBE ? "k_part_scatter + k_part_probe"
-                         : kind == K_IDX_PART ? "k_idx_scatter + k_idx_aggregate"
-                         : kind == K_BASELINE_FAST
-                             ? (nf > 0 && baseline_fast_variant(d, fv, o.kernel_variant, n_cus) == 2 ? "k_part_scatter + k_part_aggregate"
-                                                                                                      : "k_baseline_direct")
-                             : "k_generic";
-      std::snprintf(note, sizeof(note), "%s", name);
-      route_note(note);
-    }
-    *reserved = t_plan_only ? scratch_bytes : ctx.scratch_bytes;
+    route_note(family_name(kind, d, fv, o.kernel_variant, n_cus));
+    *reserved = t_plan_only ? scratch_bytes : ctx.scratch.bytes;
     return MI355Q_OK;
   }
+
+  // ---- launch
   // a scan step is ONE kernel of tens of microseconds behind a one-row initialisation: its own event pair (k_start / k_stop,
   // recorded by the launch function) is the step's time as well — two event commands fewer on the stream, ~3 us each
-  const bool one_kernel_step = nf > 0 && (kind == K_SCAN_COUNT || kind == K_SCAN_AGG);
-  if (one_kernel_step) ev_start = ev_stop = nullptr;
-  if (ev_start) HIP_TRY(hipEventRecord(ev_start, s));
+  if (nf > 0 && (kind == K_SCAN_COUNT || kind == K_SCAN_AGG)) ev.start = ev.stop = nullptr;
+  if (ev.start) HIP_TRY(hipEventRecord(ev.start, s));
   // the partitioned member writes every row of the table itself (empty rows included)
-  const bool self_init = kind == K_BASELINE_FAST && nf > 0 &&
-                         baseline_fast_variant(d, fv, o.kernel_variant, n_cus) == 2;
+  const bool self_init = kind == K_BASELINE_FAST && nf > 0 && baseline_fast_variant(d, fv, o.kernel_variant, n_cus) == 2;
   if (!self_init) HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-
-  if (nf > 0) {
-    switch (kind) {
-      case K_SCAN_COUNT:
-        HIP_TRY(launch_scan_count(d, fv, res->buf, n_cus, s, &st));
-        break;
-      case K_SCAN_AGG:
-        HIP_TRY(launch_scan_agg(d, fv, res->buf, n_cus, s, &st));
-        break;
-      case K_PERFECT_LDS:
-        HIP_TRY(launch_perfect_lds(d, fv, res->buf, d_err, n_cus, s, &st));
-        break;
-      case K_LDS_GROUPBY:
-        HIP_TRY(launch_lds_groupby(d, fv, res->buf, d_err, n_cus, s, &st));
-        break;
-      case K_BASELINE_FAST:
-        HIP_TRY(launch_baseline_fast(d, fv, res->buf, d_err, ctx.scratch, ctx.scratch_bytes,
-                                     scratch_cap, o.kernel_variant, n_cus, s, &st));
-        break;
-      case K_IDX_PART:
-        HIP_TRY(launch_idx_partitioned(d, fv, res->buf, d_err, ctx.scratch, ctx.scratch_bytes, scratch_cap, n_cus, s, &st));
-        break;
-      case K_JOIN_SUM:
-        HIP_TRY(launch_join_sum(d, fv, res->buf, n_cus, s, &st));
-        break;
-      case K_JOIN_PART:
-        HIP_TRY(launch_join_partitioned(d, fv, res->buf, d_err, ctx.scratch, ctx.scratch_bytes, scratch_cap, n_cus,
-                                        s, &st));
-        break;
-      case K_JOIN_PROBE:
-        HIP_TRY(launch_join_probe(d, fv, pay, res->buf, d_err, ctx.scratch, ctx.scratch_bytes, scratch_cap, n_cus_probe, s,
-                                  &st));
-        break;
-      default:
-        st.kernel_name = "k_generic";
-        st.n_launches = 1;
-        if (st.k_start) HIP_TRY(hipEventRecord(st.k_start, s));
-        HIP_TRY(launch_generic(d, q.idx_target_as_key, make_row_init(q), d_cols, d_rows, nf, max_frag_rows,
-                               res->buf, d_err, n_cus, s));
-        if (st.k_stop) HIP_TRY(hipEventRecord(st.k_stop, s));
-    }
-  }
+  if (nf > 0) HIP_TRY(launch_family(kind, d, q, fv, pay, res->buf, ft.d_err, ctx.scratch, scratch_cap, o.kernel_variant, n_cus, s, &st));
   if (st.spill_counter32) {
     // the counter lives in the partition scratch, which mi355q_shard_merge_slices (or the next call) may reuse or
     // reallocate before mi355q_wait looks at it: keep a copy next to the error words
-    HIP_TRY(hipMemcpyAsync(d_err + 4, st.spill_counter32, 4, hipMemcpyDeviceToDevice, s));
-    st.spill_counter32 = (uint32_t*)(d_err + 4);
+    HIP_TRY(hipMemcpyAsync(ft.d_err + 4, st.spill_counter32, 4, hipMemcpyDeviceToDevice, s));
+    st.spill_counter32 = (uint32_t*)(ft.d_err + 4);
   }
-  if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, s));
+  if (ev.stop) HIP_TRY(hipEventRecord(ev.stop, s));
   tr.mark("launched");
 
-  TailState* tail = new (std::nothrow) TailState();
+  // ---- the tail: parked for mi355q_wait, or finished here — and the step planned again where a member gave up
+  TailState* tail = new_tail(*plan, *in, q, d, kind, st, res, ft, fv, n_cus, ev, tr.on, ctx);
   if (!tail) return MI355Q_ERR_OUT_OF_CPU_MEM;
-  tail->q = q;
-  tail->d = d;
-  tail->kind = kind;
-  tail->st = st;
-  tail->res = res;
-  tail->d_err = d_err;
-  tail->d_cols = d_cols;
-  tail->d_rows = d_rows;
-  tail->h_cols.assign(in->col_buffers, in->col_buffers + (size_t)nf * nc);
-  tail->h_rows.assign(in->num_rows, in->num_rows + nf);
-  tail->nf = nf;
-  tail->nc = nc;
-  tail->n_cus = n_cus;
-  tail->total_rows = total_rows;
-  tail->max_frag_rows = max_frag_rows;
-  tail->alg_bytes = algorithmic_bytes(*plan, *in);
-  tail->s = s;
-  tail->ev_start = ev_start;
-  tail->ev_stop = ev_stop;
-  tail->ev_pool = ev_pool;
-  tail->trace = tr.on;
-  tail->knobs = tune_knobs();
-  tail->h_ret = (int32_t*)(ctx.h_meta + ctx.meta_bytes);
-  tail->h_ret_dev = ctx.h_ret_dev;
   upload_guard.armed = false;  // (finish_step synchronises the stream; a pending step is drained before the next call)
   if (pend) {  // mi355q_execute_async: the rest runs in mi355q_wait (or before the next call on this device)
     mi355q_pending* p = new (std::nothrow) mi355q_pending();
@@ -1241,22 +1001,9 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
   ctx.meta_err_clean = code == MI355Q_OK && tail->err_words_zero;
   delete tail;
   tr.mark("synchronized");
-  if (code == kRetryNoIdx) {
+  if (code == kRetryNoIdx || code == kRetryNoLds) {
     owned.reset();
-    mi355q_exec_options o2 = o;
-    o2.flags |= MI355Q_OPT_NO_IDX_PART;
-    return execute_impl(plan, in, &o2, out, report, nullptr, nullptr);
-  }
-  if (code == kRetryNoLds) {
-    owned.reset();
-    mi355q_exec_options o2 = o;
-    // small replicas did not hold the groups: the largest replica next, then eight windows of it, then another family
-    // (skipping the windows over large inputs was measured and is worse: with <= 65536 entries the families behind them
-    // are the direct global-atomic members — BH007 at 1 B rows: 29.6 ms in eight windows, 638 ms without,
-    // profiles/r04_refbench_1b_call14.jsonl)
-    o2.flags |= !(o.flags & MI355Q_OPT_LDS_BASELINE_LARGE)     ? MI355Q_OPT_LDS_BASELINE_LARGE
-                : !(o.flags & MI355Q_OPT_LDS_BASELINE_WINDOWS) ? MI355Q_OPT_LDS_BASELINE_WINDOWS
-                                                               : MI355Q_OPT_NO_LDS_BASELINE;
+    const mi355q_exec_options o2 = retry_options(code, o);
     return execute_impl(plan, in, &o2, out, report, nullptr, nullptr);
   }
   if (code) return code;

@@ -1,6 +1,9 @@
 // api_internal.h — what the translation units of the C-ABI share (api.cpp, api_routes.cpp, api_projection.cpp,
 // api_result.cpp, api_join.cpp): the opaque handle types, the per-device workspace, and the small host-side helpers.
 // Internal to libmi355q.
+// Out of execute_impl's body since the executor became a list of stages: Workspace (one grow / release for every
+// per-device allocation), launch_stream, upload_frag_table (api.cpp, shared with the Projection), try_route; the
+// compiled-filter stages and the layout twins (api_routes.cpp); join_probe_payload (api_join.cpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -38,13 +41,21 @@ struct mi355q_join_table {
   void* pay16 = nullptr;         // the same as 16-byte entries (L2 mode of the probe)
   int64_t* pay8 = nullptr;       // one-to-one tables, L2 mode: the inner value per key slot, INT64_MIN = absent
   int64_t* pay_kkeys = nullptr;  // keyed tables: the key of every slot (pay16 / pay8 are then per slot)
-  const void* pay16_col = nullptr;
-  bool pay16_built = false, pay_col_built = false;
-  int pay16_has_nulls = 0;
-  const void* pay_col = nullptr;
-  int pay_has_nulls = 0;
+  // which inner column (address AND generation: mi355q_inputs.inner_version) each of the two payload layouts was built
+  // for — pay_lds: pay_cnt / pay_wsum / pay_wnn; pay_l2: pay16 / pay8 / pay_kkeys (join_probe_payload, api_join.cpp)
+  struct PayloadCache {
+    bool built = false;
+    const void* col = nullptr;
+    int64_t version = 0;
+    int has_nulls = 0;
+    // a cached payload is only as good as the column it was derived from: same address AND same generation
+    bool holds(const void* inner, int64_t inner_version) const { return built && (!inner || (col == inner && version == inner_version)); }
+    void invalidate() {
+      built = false;
+      col = nullptr;
+    }
+  } pay_lds, pay_l2;
   float pay_build_ms = 0.f;
-  int64_t pay_version = 0, pay16_version = 0;  // mi355q_inputs.inner_version the payloads were built for
   // a payload the probe plan then refused (built, dropped): not built again for the same column and step shape
   bool pay_refused = false;
   const void* pay_refused_col = nullptr;
@@ -106,25 +117,37 @@ int cu_count_of(int dev);
 // workload — hipMalloc/hipFree of that size costs up to a second per call), the fragment
 // pointer tables and the timing events.  Calls on one device are serialised by `mu`, like
 // the reference's per-device gpu_exec_mutex_ (ExecutionKernel.cpp:216-220).
+struct Workspace {
+  void* p = nullptr;
+  int64_t bytes = 0;
+  // at least `need` bytes (what it held is NOT kept when it grows).  A failed allocation leaves it empty and hands back
+  // HIP's code: what that means for the step, and whether the sticky error is cleared, is the caller's business
+  hipError_t grow(int64_t need) {
+    if (bytes >= need) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc(&p, (size_t)need);
+    if (e == hipSuccess) bytes = need;
+    else p = nullptr;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
 struct DeviceCtx {
   std::recursive_mutex mu;  // the packed multi-column path re-enters mi355q_execute
-  void* aux = nullptr;      // packed key column + temporary tables of that path
-  int64_t aux_bytes = 0;
-  void* wide = nullptr;     // 8-byte-slot table of a step whose result layout has 4-byte slots
-  int64_t wide_bytes = 0;
-  void* proj = nullptr;     // dense temporary columns of projected expressions (one pass of fragments)
-  int64_t proj_bytes = 0;
-  void* gather = nullptr;   // dense temporary columns of a grouped join's inner side (execute_join_gather; may nest inside proj's step)
-  int64_t gather_bytes = 0;
-  void* lattice = nullptr;  // dense INT32 key columns of a lattice-keyed step (execute_affine_twin; may nest inside both)
-  int64_t lattice_bytes = 0;
+  Workspace aux;            // packed key column + temporary tables of that path
+  Workspace wide;           // 8-byte-slot table of a step whose result layout has 4-byte slots
+  Workspace proj;           // dense temporary columns of projected expressions (one pass of fragments)
+  Workspace gather;         // dense temporary columns of a grouped join's inner side (execute_join_gather; may nest inside proj's step)
+  Workspace lattice;        // dense INT32 key columns of a lattice-keyed step (execute_affine_twin; may nest inside both)
   void* bf_table = nullptr; // a compiled filter in device memory (boolfilter.h BoolFilter: atoms + truth table)
-  void* maskws = nullptr;   // the row mask of a compiled filter with program atoms (execute_masked: one pass of fragments)
-  int64_t maskws_bytes = 0;
-  void* projws = nullptr;   // Projection family: lowered expressions, ticket / total counters, tile table, tile descriptors
-  int64_t projws_bytes = 0;
-  void* scratch = nullptr;
-  int64_t scratch_bytes = 0;
+  Workspace maskws;         // the row mask of a compiled filter with program atoms (execute_masked: one pass of fragments)
+  Workspace projws;         // Projection family: lowered expressions, ticket / total counters, tile table, tile descriptors
+  Workspace scratch;        // the partition scratch
   void* meta = nullptr;
   size_t meta_bytes = 0;
   // pinned host mirror of `meta` (column table, row counts, zeroed error words go to the device as ONE copy that does not
@@ -141,6 +164,30 @@ struct DeviceCtx {
   struct mi355q_pending* inflight = nullptr;  // a step enqueued by mi355q_execute_async and not yet waited for
 };
 DeviceCtx& ctx_of(int dev);
+
+// the stream a step's work goes to: the caller's, else the context's own, created on first use (ctx.mu held)
+inline int32_t launch_stream(DeviceCtx& ctx, void* callers_stream, hipStream_t* s) {
+  *s = (hipStream_t)callers_stream;
+  if (*s) return MI355Q_OK;
+  if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
+  *s = ctx.stream;
+  return MI355Q_OK;
+}
+
+// The fragment table of a step in ctx.meta: column pointers | row counts | 64 zeroed error bytes, laid out in the pinned
+// mirror ctx.h_meta and sent as ONE copy on the launch stream (api.cpp; ctx.mu held).
+struct FragTable {
+  const int8_t* const* d_cols = nullptr;
+  const int64_t* d_rows = nullptr;
+  int32_t* d_err = nullptr;
+  hipStream_t s = nullptr;  // launch_stream(ctx, callers_stream)
+};
+enum class FragUpload {
+  kAlways,          // the Projection: sends the table every time and forgets what `meta` held
+  kSkipUnchanged,   // execute_impl: the same table as the last upload with its error words still zero is not sent again
+  kNone,            // execute_impl in RESERVE mode: lay out only, nothing is launched
+};
+int32_t upload_frag_table(DeviceCtx& ctx, const mi355q_inputs& in, int nc, void* callers_stream, FragUpload mode, FragTable* ft);
 
 
 // an owned result handle: freed with mi355q_result_free unless released to the caller
@@ -173,7 +220,7 @@ struct RouteScope {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   int32_t status = MI355Q_OK;
   RouteScope(int32_t device_id, void* stream) : dev(device_id), ctx(ctx_of(device_id)), lock(ctx.mu) {
-    status = dev.ok ? pick_stream((hipStream_t)stream) : MI355Q_ERR_HIP;
+    status = dev.ok ? launch_stream(ctx, stream, &s) : MI355Q_ERR_HIP;
   }
   RouteScope(const RouteScope&) = delete;
   ~RouteScope() {
@@ -218,32 +265,60 @@ struct RouteScope {
     }
     return MI355Q_OK;
   }
-  int32_t pick_stream(hipStream_t callers) {
-    s = callers;
-    if (!s) {
-      if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-      s = ctx.stream;
-    }
-    return MI355Q_OK;
-  }
 };
 
 constexpr int32_t kNotTaken = INT32_MIN + 7;           // internal: "use the ordinary path"
 constexpr int64_t kIdxPartMinRows = (int64_t)8 << 20;  // below this the row kernel / LDS members are as good
+// the L2 members of the payload probe map workgroup b to XCD b % 8 and group b / 8 and walk the runs with stride
+// gridDim / 8: they are planned and launched with a multiple of 8 workgroups, or not at all (found by the host
+// simulation, which first ran them on "4 CUs": gridDim / 8 = 0 never advances — on the device a `tune_cus` below 8
+// would have hung the GPU, and one that is not a multiple of 8 would have read some runs twice)
+inline int probe_cus(int n_cus) { return n_cus >= 8 ? (n_cus & ~7) : 0; }
+
+// Asks one route: what it answers, or kNotTaken with everything it noted for mi355q_explain cut back and *out null
+// again, so that the next route in the order starts from a clean slate.  unsupported_too: execute_multi_value's one
+// extra — its MI355Q_ERR_UNSUPPORTED means "not this way" as well.
+// Every route is asked through here, which made three former hand-written undos uniform; none of them changes anything:
+//  - execute_shifted_args and execute_cast_key used not to null *out.  Both store to *out only as their last statement
+//    before `return MI355Q_OK`, or through an inner execute_impl, which nulls *out on entry and stores to it only where
+//    it returns MI355Q_OK: behind a kNotTaken *out still is the null execute_impl laid down on entry.
+//  - execute_affine_twin used to take no mark.  It is asked only where `reserved` is null, and t_route is non-null only
+//    inside mi355q_explain, which plans with `reserved` set, as does every step a route derives while planning: with
+//    t_route null there is nothing to mark or cut.
+template <class Route>
+int32_t try_route(mi355q_result** out, Route&& route, bool unsupported_too = false) {
+  const size_t mark = t_route ? t_route->size() : 0;
+  const int32_t e = route();
+  if (e != kNotTaken && !(unsupported_too && e == MI355Q_ERR_UNSUPPORTED)) return e;
+  if (t_route) t_route->resize(mark);
+  *out = nullptr;
+  return kNotTaken;
+}
 
 // the step executor (api.cpp).  reserved != null: RESERVE mode, plan only; pend != null: mi355q_execute_async
 int32_t execute_impl(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options* opts, mi355q_result** out,
                      mi355q_exec_report* report, mi355q_pending** pend, int64_t* reserved = nullptr);
 // ---- the derived-plan routes (api_routes.cpp), in execute_impl's order of asking.  Each rewrites the stated plan into a
 // simpler one, runs that through mi355q_execute and fixes the result up; kNotTaken when the shape does not call for it.
-int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const BoolFilterHost& bfh, const mi355q_inputs* in,
-                       const mi355q_exec_options& o, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+// (the compiled-filter stages: an aggregate step's filter — fused atoms, else programs through the row mask —, a
+// Projection whose expressions all belong to its filter, several plain quals in front of a one-filter family)
+int32_t execute_compiled_filter(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                                mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_projection_filter(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                                  mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_compiled_quals(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                               mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_shifted_args(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
                              mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_cast_key(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
                          mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_projected(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
                           mi355q_result** out, mi355q_exec_report* report);
+// (the layout twins: columnar output through its row-wise form, 4-byte slots through the 8-byte layout)
+int32_t execute_columnar_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                              mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+int32_t execute_wide_slot_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                               mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_dense_join_as_filter(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
                                      mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
@@ -275,6 +350,10 @@ struct RowTwin {
 int32_t make_row_twin(const mi355q_result* r, hipStream_t s, RowTwin* out);
 int32_t store_row_twin(const RowTwin& t, mi355q_result* r, hipStream_t s);
 int32_t run_reduce(mi355q_result* dst, const int64_t* rows, int64_t n_rows, void* stream);
+// (api_join.cpp) the payload of the payload probe for this step, built on first use and cached with the join table:
+// true with *pay filled when the probe is to run the step, false when it is not (no such shape, refused, out of memory)
+bool join_probe_payload(mi355q_join_table* jt, const DevPlan& d, const FragView& fv, int64_t inner_version, hipStream_t s,
+                        int n_cus, JoinPayloadView* pay);
 int32_t attach_join(const mi355q_plan& p, const mi355q_inputs* in, DevPlan* d);  // (api.cpp) the join table and the inner columns
 int64_t projection_row_count(const mi355q_result* r);
 int32_t projection_append(mi355q_result* this_rs, const mi355q_result* that_rs, hipStream_t s);

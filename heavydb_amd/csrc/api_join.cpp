@@ -19,6 +19,100 @@
 using namespace mq;
 using namespace mq::api;
 
+// ------------------------------------------------------------------------------- the payload probe's payload
+// Joins that read the inner side / one-to-many tables / LEFT joins over a large outer table: the payload probe (per-key
+// aggregated payload of the perfect table in LDS, or in L2 as 16-byte entries).  The payload is derived from ONE inner
+// column on first use and kept with the join table; a payload the probe plan then refuses is dropped and not built
+// again for the same column and step shape.  The first build waits for the device (flags read-back).
+bool mq::api::join_probe_payload(mi355q_join_table* jt, const DevPlan& d, const FragView& fv, int64_t inner_version,
+                                 hipStream_t s, int n_cus, JoinPayloadView* pay) {
+  const int n_cus_probe = probe_cus(n_cus);
+  int wcol = -1, l2 = 0;
+  if (!n_cus_probe || !join_probe_wants(d, fv, n_cus_probe, &wcol, &l2)) return false;
+  const void* inner = wcol >= 0 ? (const void*)d.inner_cols[wcol] : nullptr;
+  std::lock_guard<std::mutex> pl(jt->pay_mu);
+  const int64_t entries = jt->entry_count;
+  if (jt->pay_refused && jt->pay_refused_col == inner && jt->pay_refused_rows == fv.total_rows) return false;
+  mi355q_join_table::PayloadCache& cache = l2 ? jt->pay_l2 : jt->pay_lds;
+  if (!cache.holds(inner, inner_version)) {
+    // (re)build for this inner column, in the layout the chosen mode reads
+    hipEvent_t b0 = nullptr, b1 = nullptr;
+    (void)hipEventCreate(&b0);
+    (void)hipEventCreate(&b1);
+    DevWord flags;
+    bool ok = hipMalloc(&flags.p, 64) == hipSuccess;
+    if (l2) {
+      if (ok && !jt->pay16) ok = hipMalloc(&jt->pay16, (size_t)entries * 16) == hipSuccess;
+      // one-to-one tables: the 8-byte payload — interleaved with the slot's key for a keyed table
+      if (ok && (jt->hash_type == 0 || jt->hash_type == 1) && !jt->pay8)
+        ok = hipMalloc((void**)&jt->pay8, (size_t)entries * (l2 == 2 ? 16 : 8)) == hipSuccess;
+      // (one spare key behind the end: the keyed probe reads the keys two at a time)
+      if (ok && l2 == 2 && !jt->pay_kkeys) ok = hipMalloc((void**)&jt->pay_kkeys, (size_t)entries * 8 + 16) == hipSuccess;
+    } else {
+      if (ok && !jt->pay_cnt) ok = hipMalloc((void**)&jt->pay_cnt, (size_t)entries * 4) == hipSuccess;
+      if (ok && inner && !jt->pay_wsum) ok = hipMalloc((void**)&jt->pay_wsum, (size_t)entries * 8) == hipSuccess;
+      if (ok && inner && !jt->pay_wnn) ok = hipMalloc((void**)&jt->pay_wnn, (size_t)entries * 4) == hipSuccess;
+    }
+    if (ok) {
+      (void)hipMemsetAsync(flags.p, 0, 64, s);
+      if (b0) (void)hipEventRecord(b0, s);
+      ok = (l2 == 2 ? launch_join_payload_keyed_build(jt->buf, jt->hash_type, entries, inner, jt->pay_kkeys, jt->pay16,
+                                                      jt->pay8, (int32_t*)flags.p, n_cus, s)
+                    : launch_join_payload_build(jt->buf, jt->hash_type, entries, inner, jt->pay_cnt, jt->pay_wsum,
+                                                jt->pay_wnn, l2 ? jt->pay16 : nullptr, l2 ? jt->pay8 : nullptr,
+                                                (int32_t*)flags.p, n_cus, s)) == hipSuccess;
+      if (b1) (void)hipEventRecord(b1, s);
+      int32_t h_flags = 0;
+      ok = ok && hipMemcpyAsync(&h_flags, flags.p, 4, hipMemcpyDeviceToHost, s) == hipSuccess &&
+           hipStreamSynchronize(s) == hipSuccess;
+      if (ok) {
+        cache.built = true;
+        cache.col = inner;
+        cache.version = inner_version;
+        cache.has_nulls = h_flags & 1;
+        if (b0 && b1) (void)hipEventElapsedTime(&jt->pay_build_ms, b0, b1);
+      }
+    }
+    if (b0) (void)hipEventDestroy(b0);
+    if (b1) (void)hipEventDestroy(b1);
+    if (!ok) {
+      (void)hipGetLastError();
+      return false;
+    }
+  }
+  pay->cnt_k = l2 ? nullptr : jt->pay_cnt;
+  pay->wsum_k = (!l2 && inner) ? jt->pay_wsum : nullptr;
+  pay->wnn_k = (!l2 && inner) ? jt->pay_wnn : nullptr;
+  pay->pay16 = l2 ? jt->pay16 : nullptr;
+  pay->pay8 = l2 ? jt->pay8 : nullptr;
+  pay->kkeys = l2 == 2 ? jt->pay_kkeys : nullptr;
+  pay->inner_col = inner;
+  pay->entries = entries;
+  pay->has_nulls = cache.has_nulls;
+  if (join_probe_supported(d, fv, *pay, n_cus_probe)) return true;
+  // the probe plan does not take this payload after all: entries x 16 B of device memory are not kept for a
+  // member that will not run (the step falls back to k_join_sum / the row kernel)
+  auto drop = [](auto*& ptr) {
+    if (ptr) (void)hipFree((void*)ptr);
+    ptr = nullptr;
+  };
+  if (l2) {
+    drop(jt->pay16);
+    drop(jt->pay8);
+    drop(jt->pay_kkeys);
+  } else {
+    drop(jt->pay_cnt);
+    drop(jt->pay_wsum);
+    drop(jt->pay_wnn);
+  }
+  cache.invalidate();
+  *pay = JoinPayloadView{};
+  jt->pay_refused = true;
+  jt->pay_refused_col = inner;
+  jt->pay_refused_rows = fv.total_rows;
+  return false;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------- joins
@@ -169,10 +263,8 @@ int32_t mi355q_join_invalidate_payload(mi355q_join_table* t) {
   if (!t) return MI355Q_ERR_INVALID_PLAN;
   std::lock_guard<std::mutex> pl(t->pay_mu);
   // the buffers are kept (the next build reuses them); only their validity goes
-  t->pay16_built = false;
-  t->pay_col_built = false;
-  t->pay16_col = nullptr;
-  t->pay_col = nullptr;
+  t->pay_l2.invalidate();
+  t->pay_lds.invalidate();
   t->pay_refused = false;
   return MI355Q_OK;
 }
@@ -191,7 +283,7 @@ int32_t mi355q_join_payload_info(const mi355q_join_table* t, int64_t* bytes, flo
   if (t->pay_kkeys) b += n * 8;
   if (bytes) *bytes = b;
   if (build_ms) *build_ms = t->pay_build_ms;
-  if (inner_version) *inner_version = t->pay16_built ? t->pay16_version : t->pay_version;
+  if (inner_version) *inner_version = t->pay_l2.built ? t->pay_l2.version : t->pay_lds.version;
   return MI355Q_OK;
 }
 

@@ -109,56 +109,23 @@ int32_t execute_projection(const mi355q_plan* plan, const mi355q_inputs* in, con
   const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
   DeviceCtx& ctx = ctx_of(in->device_id);
   std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
-  if (ctx.projws_bytes < ws_need) {
-    if (ctx.projws) (void)hipFree(ctx.projws);
-    ctx.projws = nullptr;
-    ctx.projws_bytes = 0;
-    HIP_TRY(hipMalloc(&ctx.projws, (size_t)ws_need));
-    ctx.projws_bytes = ws_need;
-  }
+  HIP_TRY(ctx.projws.grow(ws_need));
   if (reserved) return MI355Q_OK;
 
-  hipStream_t s = (hipStream_t)o.stream;
-  if (!s) {
-    if (!ctx.stream) HIP_TRY(hipStreamCreateWithFlags(&ctx.stream, hipStreamNonBlocking));
-    s = ctx.stream;
-  }
-  // column table | row counts | error word, one upload out of pinned memory
-  const size_t ptr_bytes = sizeof(void*) * (size_t)std::max(1, nf * nc);
-  const size_t rows_bytes = sizeof(int64_t) * (size_t)std::max(1, nf);
-  const size_t meta_bytes = ptr_bytes + rows_bytes + 64;
-  if (ctx.meta_bytes < meta_bytes) {
-    if (ctx.meta) (void)hipFree(ctx.meta);
-    ctx.meta = nullptr;
-    ctx.meta_bytes = 0;
-    if (ctx.h_meta) (void)hipHostFree(ctx.h_meta);
-    ctx.h_meta = nullptr;
-    ctx.h_ret_dev = nullptr;
-    HIP_TRY(hipMalloc(&ctx.meta, meta_bytes * 2));
-    HIP_TRY(hipHostMalloc((void**)&ctx.h_meta, meta_bytes * 2 + 64, hipHostMallocDefault));
-    ctx.meta_bytes = meta_bytes * 2;
-  }
-  char* mp = (char*)ctx.meta;
-  const int8_t* const* d_cols = (const int8_t* const*)mp;
-  const int64_t* d_rows = (const int64_t*)(mp + ptr_bytes);
-  int32_t* d_err = (int32_t*)(mp + ptr_bytes + rows_bytes);
-  {
-    char* hm = ctx.h_meta;
-    if (nf > 0) {
-      std::memcpy(hm, in->col_buffers, sizeof(void*) * (size_t)(nf * nc));
-      std::memcpy(hm + ptr_bytes, in->num_rows, sizeof(int64_t) * (size_t)nf);
-    }
-    std::memset(hm + ptr_bytes + rows_bytes, 0, 64);
-    const size_t lo = nf > 0 ? 0 : ptr_bytes + rows_bytes;
-    ctx.meta_shadow.clear();  // (execute_impl's record of what `meta` holds)
-    ctx.meta_err_clean = false;
-    HIP_TRY(hipMemcpyAsync(mp + lo, hm + lo, ptr_bytes + rows_bytes + 64 - lo, hipMemcpyHostToDevice, s));
-  }
+  // column table | row counts | error word, one upload out of pinned memory (always sent: the table of a Projection is
+  // not remembered)
+  FragTable ft;
+  if (int32_t e = launch_stream(ctx, o.stream, &ft.s)) return e;
+  if (int32_t e = upload_frag_table(ctx, *in, nc, ft.s, FragUpload::kAlways, &ft)) return e;
+  hipStream_t s = ft.s;
+  const int8_t* const* d_cols = ft.d_cols;
+  const int64_t* d_rows = ft.d_rows;
+  int32_t* d_err = ft.d_err;
   const DevExprSet* d_xs = nullptr;
   if (plan->n_exprs != 0) {
-    HIP_TRY(hipMemcpyAsync(ctx.projws, &xs, sizeof(xs), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx.projws.p, &xs, sizeof(xs), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));  // (xs lives on this frame)
-    d_xs = (const DevExprSet*)ctx.projws;
+    d_xs = (const DevExprSet*)ctx.projws.p;
   }
 
   mi355q_result* res = nullptr;
@@ -181,7 +148,7 @@ int32_t execute_projection(const mi355q_plan* plan, const mi355q_inputs* in, con
   FragView fv{d_cols, d_rows, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
   if (ev_start) HIP_TRY(hipEventRecord(ev_start, s));
   unsigned long long* d_total = nullptr;
-  HIP_TRY(launch_projection(d, ps, d_xs, qmask, fv, (char*)ctx.projws + kExprArea, res->buf, d_err, &d_total, n_cus, s, &st, &forms));
+  HIP_TRY(launch_projection(d, ps, d_xs, qmask, fv, (char*)ctx.projws.p + kExprArea, res->buf, d_err, &d_total, n_cus, s, &st, &forms));
   if (ev_stop) HIP_TRY(hipEventRecord(ev_stop, s));
   // the error word and the match count come back together
   int64_t* h_ret = (int64_t*)(ctx.h_meta + ctx.meta_bytes);

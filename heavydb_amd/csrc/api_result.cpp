@@ -689,19 +689,13 @@ int32_t mi355q_shard_merge_slices(mi355q_result* r, const void* const* slices, c
   const int n_cus = cu_count_of(r->device_id);
   const int64_t need = slice_merge_scratch_bytes(r->dplan, home_lo, home_hi, n_cus);
   if (need == 0) return MI355Q_ERR_UNSUPPORTED;  // the caller folds with mi355q_shard_merge_range
-  if (need + 64 > ctx.scratch_bytes) {
-    if (ctx.scratch) (void)hipFree(ctx.scratch);
-    ctx.scratch = nullptr;
-    ctx.scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&ctx.scratch, (size_t)need + 64));
-    ctx.scratch_bytes = need + 64;
-  }
+  HIP_TRY(ctx.scratch.grow(need + 64));
   hipStream_t s = (hipStream_t)stream;
   // the error word: the last 64 bytes of the workspace
-  int32_t* d_err = (int32_t*)((char*)ctx.scratch + ((need + 7) & ~(int64_t)7));
+  int32_t* d_err = (int32_t*)((char*)ctx.scratch.p + ((need + 7) & ~(int64_t)7));
   HIP_TRY(hipMemsetAsync(d_err, 0, 2 * sizeof(int32_t), s));
   HIP_TRY(launch_slice_merge(r->dplan, r->buf, (const int64_t* const*)slices, pads && pad_rows > 0 ? (const int64_t* const*)pads : nullptr,
-                             n_src, pad_rows, home_lo, home_hi, d_err, ctx.scratch, need, n_cus, s));
+                             n_src, pad_rows, home_lo, home_hi, d_err, ctx.scratch.p, need, n_cus, s));
   int32_t h_err[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));

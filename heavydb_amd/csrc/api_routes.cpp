@@ -34,8 +34,7 @@ int64_t pass_budget(int64_t held_bytes) {
 //   column chunks | pointer table | bytes_after_tab | row counts | 256 (64 error bytes) | bytes_after_err
 struct PassLoop {
   // ---- stated by the route
-  void*& ws;                       // the DeviceCtx workspace pair to grow
-  int64_t& ws_bytes;
+  Workspace& ws;                   // the DeviceCtx workspace to grow
   int nc;                          // stated columns; the temporary ones follow them in the derived step's table
   int n_extra;                     // temporary columns
   const int32_t* width;            // their widths in bytes
@@ -73,14 +72,14 @@ struct PassLoop {
   ResultPtr res;                   // all passes folded
   mi355q_exec_report acc{};
 
-  PassLoop(void*& ws_, int64_t& ws_bytes_, int nc_, int n_extra_, const int32_t* width_, const mi355q_plan* derived_)
-      : ws(ws_), ws_bytes(ws_bytes_), nc(nc_), n_extra(n_extra_), width(width_), derived(derived_) {}
+  PassLoop(Workspace& ws_, int nc_, int n_extra_, const int32_t* width_, const mi355q_plan* derived_)
+      : ws(ws_), nc(nc_), n_extra(n_extra_), width(width_), derived(derived_) {}
 
   // sizes a pass from the free memory (o.pass_rows: the tests' override) and grows the workspace to hold it
   int32_t prepare(const mi355q_inputs* in, const mi355q_exec_options& o, int64_t total_rows, int64_t max_frag_rows) {
     const int nf = in->n_frags;
     nc2 = nc + n_extra;
-    const int64_t budget = pass_budget(ws_bytes);
+    const int64_t budget = pass_budget(ws.bytes);
     int64_t row_bytes = 0;
     for (int k = 0; k < n_extra; ++k) row_bytes += width[k];
     // every (fragment, column) chunk starts on a 16-byte boundary: the fast families want aligned columns
@@ -93,19 +92,12 @@ struct PassLoop {
     const int64_t rows_bytes = ((int64_t)sizeof(int64_t) * nf + 255) & ~255ll;
     col_region = ((pass_rows * row_bytes + pad * nf) + 255) & ~255ll;
     const int64_t need = col_region + tab_bytes + bytes_after_tab + rows_bytes + 256 + bytes_after_err;
-    if (ws_bytes < need) {
-      if (ws) (void)hipFree(ws);
-      ws = nullptr;
-      ws_bytes = 0;
-      const hipError_t he = hipMalloc(&ws, (size_t)need);
-      if (he != hipSuccess) {
-        if (alloc_failed != kNotTaken) last_hip_error = he;
-        (void)hipGetLastError();
-        return alloc_failed;
-      }
-      ws_bytes = need;
+    if (const hipError_t he = ws.grow(need)) {
+      if (alloc_failed != kNotTaken) last_hip_error = he;
+      (void)hipGetLastError();
+      return alloc_failed;
     }
-    base = (char*)ws;
+    base = (char*)ws.p;
     d_tab = (const int8_t**)(base + col_region);
     after_tab = base + col_region + tab_bytes;
     d_rows = (int64_t*)(after_tab + bytes_after_tab);
@@ -410,7 +402,7 @@ int32_t execute_packed_multi(const mi355q_plan* plan, const mi355q_inputs* in, c
   hipStream_t s = rs.s;
   // memory: two temporary tables + the packed column of one pass (a group of fragments)
   const int64_t tmp_bytes = (q2.entry_count * (int64_t)q2.row_size + 255) & ~255ll;
-  int64_t pass_rows = pass_budget(ctx.aux_bytes) / 8;
+  int64_t pass_rows = pass_budget(ctx.aux.bytes) / 8;
   if (o.pass_rows > 0 && o.pass_rows < pass_rows)  // tests: force several passes
     pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);
   if (pass_rows < max_frag_rows + 2 * (int64_t)nf) return kNotTaken;
@@ -418,17 +410,11 @@ int32_t execute_packed_multi(const mi355q_plan* plan, const mi355q_inputs* in, c
   const int64_t pack_bytes = ((pass_rows + 2 * (int64_t)nf) * 8 + 255) & ~255ll;
   const int64_t tab_bytes = sizeof(void*) * (size_t)nf;
   const int64_t need = pack_bytes + 2 * tmp_bytes + ((tab_bytes + 255) & ~255ll) + 256;
-  if (ctx.aux_bytes < need) {
-    if (ctx.aux) (void)hipFree(ctx.aux);
-    ctx.aux = nullptr;
-    ctx.aux_bytes = 0;
-    if (hipMalloc(&ctx.aux, (size_t)need) != hipSuccess) {
-      (void)hipGetLastError();
-      return kNotTaken;
-    }
-    ctx.aux_bytes = need;
+  if (ctx.aux.grow(need) != hipSuccess) {
+    (void)hipGetLastError();
+    return kNotTaken;
   }
-  char* aux = (char*)ctx.aux;
+  char* aux = (char*)ctx.aux.p;
   int64_t* packed = (int64_t*)aux;
   int64_t* tmp_a = (int64_t*)(aux + pack_bytes);
   int64_t* tmp_b = (int64_t*)(aux + pack_bytes + tmp_bytes);
@@ -698,7 +684,7 @@ int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, co
   if (inner_join) width[n_used] = 4;  // (the matched flag, behind the gathered columns)
   mi355q_inputs in_outer = *in;       // the derived step has no inner side
   in_outer.inner_col_buffers = nullptr;
-  PassLoop pl(rs.ctx.gather, rs.ctx.gather_bytes, nc, nc2 - nc, width, &p2);
+  PassLoop pl(rs.ctx.gather, nc, nc2 - nc, width, &p2);
   pl.clear_err_word = false;
   if (int32_t e = pl.prepare(&in_outer, o, total_rows, max_frag_rows)) return e;
   if (int32_t e = pl.run(rs, &in_outer, o, report, [&](int f, int pnf) -> int32_t {
@@ -973,7 +959,7 @@ int32_t execute_affine_twin(const mi355q_plan* plan, const mi355q_inputs* in, co
   // ---- passes: lattice indices of a pass of fragments, the twin step on them
   int32_t w4[MI355Q_MAX_GROUP_COLS];
   for (int k = 0; k < n_proj; ++k) w4[k] = 4;
-  PassLoop pl(rs.ctx.lattice, rs.ctx.lattice_bytes, nc, n_proj, w4, &p2);
+  PassLoop pl(rs.ctx.lattice, nc, n_proj, w4, &p2);
   pl.first_into_out_buffer = false;
   pl.inner_errors_not_taken = true;
   pl.twin = &q2;
@@ -1313,7 +1299,7 @@ int32_t execute_projected(const mi355q_plan* plan, const mi355q_inputs* in, cons
   if (rs.status) return rs.status;
   const int n_cus = cu_count_of(in->device_id);
   hipStream_t s = rs.s;
-  PassLoop pl(rs.ctx.proj, rs.ctx.proj_bytes, nc, nx, widths, &lp);
+  PassLoop pl(rs.ctx.proj, nc, nx, widths, &lp);
   pl.bytes_after_err = ((int64_t)sizeof(DevExprSet) + 255) & ~255ll;  // the lowered programs, read by k_project from device memory
   pl.alloc_failed = MI355Q_ERR_OUT_OF_GPU_MEM;
   pl.count_pre_pass = false;
@@ -1388,7 +1374,7 @@ int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const B
   hipStream_t s = rs.s;
   // one pass of fragments = as many as the mask region holds (1 B/row: 16 GB of it cover 16 G rows)
   const int32_t mask_width = 1;
-  PassLoop pl(ctx.maskws, ctx.maskws_bytes, nc, 1, &mask_width, &mp);
+  PassLoop pl(ctx.maskws, nc, 1, &mask_width, &mp);
   pl.mask_column = true;
   pl.bytes_after_tab = ((int64_t)sizeof(void*) * nf + 255) & ~255ll;  // per fragment: its mask chunk
   pl.alloc_failed = MI355Q_ERR_OUT_OF_GPU_MEM;
@@ -1416,6 +1402,169 @@ int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const B
     return e;
   if (int32_t e = rs.finish_sync_if_timed(report, pl.acc, *plan, *in, total_rows)) return e;
   *out = pl.res.release();
+  return MI355Q_OK;
+}
+
+// ------------------------------------------------------------------------------- the compiled-filter stages
+// A filter of comparisons with literals under AND / OR / NOT is compiled into atoms + a truth table and evaluated by
+// the consuming kernel on the values it holds in registers (boolfilter.h): no temporary column, no second pass.
+namespace {
+
+struct BfScope {  // the compiled filter travels beside the plan for the duration of one inner step
+  BfScope(const BoolFilter* host, const BoolFilter* dev) { set_step_bool_filter(host, dev); }
+  ~BfScope() { set_step_bool_filter(nullptr, nullptr); }
+};
+
+// atoms (and the few lean programs the LDS members evaluate themselves) inside the consuming family: the filter goes to
+// ctx.bf_table and `rest` runs with it beside the plan; kNotTaken when no family that takes a filter takes the step
+int32_t execute_fused_filter(const mi355q_plan& rest, const BoolFilterHost& bfh, const mi355q_inputs* in, const mi355q_exec_options& o,
+                             mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  DeviceGuard gb(in->device_id);
+  DeviceCtx& cb = ctx_of(in->device_id);
+  std::lock_guard<std::recursive_mutex> lb(cb.mu);
+  bool have = true;
+  if (!t_plan_only) {
+    if (!cb.bf_table) have = gb.ok && hipMalloc(&cb.bf_table, sizeof(BoolFilter)) == hipSuccess;
+    // (a synchronous copy out of this frame: atoms + truth table, 1.2 KB)
+    have = have && hipMemcpy(cb.bf_table, &bfh.bf, sizeof(BoolFilter), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!have) {
+    (void)hipGetLastError();
+    return kNotTaken;
+  }
+  BfScope scope(&bfh.bf, (const BoolFilter*)cb.bf_table);
+  route_note("filter compiled (atoms + truth table)");
+  return execute_impl(&rest, in, &o, out, report, nullptr, reserved);
+}
+
+}  // namespace
+
+// the filter of an aggregate step with expressions: fused into the consuming family where one takes it, else — program
+// atoms no family evaluates itself — the row-mask pre-pass, then `mask = 1`
+int32_t execute_compiled_filter(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                                mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  BoolFilterHost bfh;
+  mi355q_plan rest;
+  if (!compile_bool_filter(*plan, &bfh, &rest)) return kNotTaken;
+  int32_t e = kNotTaken;
+  const bool fused_progs = bfh.bf.n_progs == 0 || (bfh.bf.all_lean && bfh.bf.all_i32 && bfh.bf.n_progs <= kLdsFusedProgs &&
+                                                   !(o.flags & MI355Q_OPT_FILTER_PREPASS));
+  if (fused_progs) e = try_route(out, [&] { return execute_fused_filter(rest, bfh, in, o, out, report, reserved); });
+  if (e == kNotTaken && bfh.bf.n_progs != 0)
+    e = try_route(out, [&] {
+      route_note("filter compiled (atoms + programs + truth table)");
+      return execute_masked(plan, rest, bfh, in, o, out, report, reserved);
+    });
+  if (e == MI355Q_OK && report && !reserved) report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
+  return e;
+}
+
+// a Projection whose expressions all belong to the FILTER (`SELECT a, b FROM t WHERE x + y > 100`): the filter is compiled,
+// the row-mask pre-pass evaluates it, the Projection runs on `mask = 1` — in its fast member where the targets allow —
+// instead of evaluating the quals' expressions row by row in the general member.  With a LIMIT only where the filter
+// cannot raise: the pre-pass looks at every row, the reference's loop stops at the limit.
+int32_t execute_projection_filter(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                                  mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  BoolFilterHost bfh;
+  mi355q_plan rest;
+  if (!compile_bool_filter(*plan, &bfh, &rest) || (bfh.bf.any_raise && plan->scan_limit != 0)) return kNotTaken;
+  return try_route(out, [&] {
+    route_note("filter compiled (atoms + programs + truth table)");
+    return execute_masked(plan, rest, bfh, in, o, out, report, reserved);
+  });
+}
+
+// SEVERAL plain quals in front of a family that filters on one column (the partitioned GROUP BY, the perfect-hash LDS
+// member, the index-partitioned family takes none): instead of the row kernel, the quals become the range atoms of a
+// compiled filter, the row-mask pre-pass evaluates them (k_filter_mask: one byte per row) and the step runs on
+// `mask = 1` — measured in round 6: `a < K AND b > L` over 10 M INT64 groups went to k_generic at 55 ms per 1 B rows
+int32_t execute_compiled_quals(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                               mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  BoolFilterHost bfh;
+  mi355q_plan rest;
+  if (!compile_bool_filter(*plan, &bfh, &rest)) return kNotTaken;
+  return try_route(out, [&] {
+    route_note("quals compiled (range atoms + truth table)");
+    return execute_masked(plan, rest, bfh, in, o, out, report, reserved);
+  });
+}
+
+// ------------------------------------------------------------------------------- the layout twins
+// Columnar output: the step runs on the row-wise form of the same decisions (same entry count, 8-byte key components,
+// same hash, same slots) into a library-owned table, and the finished table is moved column by column into the
+// caller-visible buffer.
+// Known oddity, kept as it was in execute_impl: unlike every other route this one takes neither the context lock nor
+// the context's stream — the inner step locks for itself, and store_row_twin runs on the CALLER's stream, the null
+// stream where the caller gave none.
+int32_t execute_columnar_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                              mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  mi355q_plan pr = *plan;
+  pr.output_columnar_hint = MI355Q_OUTPUT_ROWWISE_COLUMNAR_DECISIONS;
+  mi355q_exec_options orw = o;
+  orw.out_buffer = nullptr;
+  if (reserved) {
+    route_note("row-wise twin + k_rows_to_columns");
+    return execute_impl(&pr, in, &orw, out, report, nullptr, reserved);
+  }
+  RowTwin t;
+  if (int32_t e = mi355q_execute(&pr, in, &orw, &t.tw, report)) return e;
+  const mi355q_qmd& qr = t.tw->qmd;
+  if (qr.entry_count != q.entry_count || qr.row_size != q.row_size || qr.key_bytes != q.key_bytes ||
+      qr.slot_count != q.slot_count || qr.slot_width != q.slot_width || qr.output_columnar)
+    return MI355Q_ERR_UNSUPPORTED;
+  mi355q_result* rc = nullptr;
+  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &rc)) return e;
+  if (int32_t e = store_row_twin(t, rc, (hipStream_t)o.stream)) {
+    mi355q_result_free(rc);
+    return e;
+  }
+  *out = rc;
+  return MI355Q_OK;
+}
+
+// Compact layout (4-byte slots): the step runs on the 8-byte layout of the same plan — same entry count, same key
+// bytes, same hash — into ctx.wide, and the finished table is narrowed row by row.
+int32_t execute_wide_slot_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                               mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  int64_t rows = 0;
+  for (int f = 0; f < in->n_frags; ++f) rows += in->num_rows[f];
+  if (rows > (int64_t)UINT32_MAX) return MI355Q_ERR_INVALID_PLAN;  // a 32-bit COUNT would wrap
+  mi355q_plan p8 = *plan;
+  p8.bigint_count = 1;  // pick_target_compact_width: g_bigint_count -> 8-byte slots
+  mi355q_qmd q8;
+  if (int32_t e = qmd_init(p8, &q8)) return e;
+  if (q8.slot_width != 8 || q8.entry_count != q.entry_count || q8.key_bytes != q.key_bytes ||
+      q8.slot_count != q.slot_count)
+    return MI355Q_ERR_UNSUPPORTED;
+  if (reserved) {
+    route_note("8-byte-slot twin + k_narrow_slots");
+    return execute_impl(&p8, in, &o, out, report, nullptr, reserved);
+  }
+  DeviceCtx& ctx = ctx_of(in->device_id);
+  std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
+  if (const hipError_t he = ctx.wide.grow(q8.entry_count * (int64_t)q8.row_size)) {
+    last_hip_error = he;
+    return MI355Q_ERR_OUT_OF_GPU_MEM;
+  }
+  hipStream_t s4 = nullptr;
+  if (int32_t e = launch_stream(ctx, o.stream, &s4)) return e;
+  mi355q_exec_options o8 = o;
+  o8.stream = s4;
+  o8.out_buffer = ctx.wide.p;
+  mi355q_result* r8 = nullptr;
+  if (int32_t e = mi355q_execute(&p8, in, &o8, &r8, report)) return e;
+  mi355q_result_free(r8);
+  mi355q_result* res4 = nullptr;
+  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res4)) return e;
+  hipError_t he = launch_narrow_slots((const int64_t*)ctx.wide.p, q8.row_size / 8, q.key_bytes / 8, q.slot_count,
+                                      q.row_size / 8, q.entry_count, res4->buf, s4);
+  if (he == hipSuccess) he = hipStreamSynchronize(s4);
+  if (he != hipSuccess) {
+    last_hip_error = he;
+    mi355q_result_free(res4);
+    return MI355Q_ERR_HIP;
+  }
+  *out = res4;
   return MI355Q_OK;
 }
 

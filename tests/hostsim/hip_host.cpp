@@ -7,6 +7,7 @@
 //            after the other; kernels with __syncthreads / shuffles / ballots / LDS run the threads of a block as
 //            cooperative fibers (ucontext) that yield at a barrier — deterministic, no data races, atomics trivially
 //            atomic; per-wave (64 lanes) exchange buffers for shuffles / ballots, a dynamic LDS area
+#include <cstdarg>
 #include <ucontext.h>
 #include <unistd.h>
 
@@ -23,6 +24,21 @@
 #include <vector>
 
 #include "hip/hip_runtime.h"
+
+// HOSTSIM_CALL_LOG=<file>: every runtime call that allocates, enqueues or waits, one line each, in call order — sizes,
+// kinds, kernel names and grids, never addresses — so that two builds of the library can be compared command by command
+// (test infrastructure, beside HOSTSIM_TRACE)
+static void call_log(const char* fmt, ...) {
+  static FILE* f = std::getenv("HOSTSIM_CALL_LOG") ? std::fopen(std::getenv("HOSTSIM_CALL_LOG"), "a") : nullptr;
+  if (!f) return;
+  va_list ap;
+  va_start(ap, fmt);
+  std::vfprintf(f, fmt, ap);
+  va_end(ap);
+  std::fputc('\n', f);
+  std::fflush(f);
+}
+extern "C" void hostsim_call_log_note(const char* text) { call_log("# %s", text); }
 
 namespace hipsim {
 
@@ -234,6 +250,7 @@ void launch(const char* name, dim3 grid, dim3 block, size_t shmem, const std::fu
     std::signal(SIGALRM, watchdog);
     alarm((unsigned)wd);
   }
+  call_log("launch %s grid %u,%u,%u block %u,%u,%u lds %zu", name, grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem);
   if (trace) std::fprintf(stderr, "[hipsim] %s grid %u block %u lds %zu %s\n", name, grid.x, block.x, shmem, fibers ? "fibers" : "plain");
   for (unsigned z = 0; z < grid.z; ++z)
     for (unsigned y = 0; y < grid.y; ++y)
@@ -367,6 +384,7 @@ int hostsim_live_allocations() { return (int)g_allocs.size(); }
 hipError_t hipMalloc(void** p, size_t bytes) {
   if (!p) return hipErrorInvalidValue;
   std::lock_guard<std::mutex> lk(g_mem_mu);
+  call_log("hipMalloc %zu", bytes);
   if (bytes > g_fail_after || g_used + bytes > kTotal) {
     *p = nullptr;
     return hipErrorOutOfMemory;
@@ -388,13 +406,15 @@ hipError_t hipFree(void* p) {
     std::fprintf(stderr, "hipsim: hipFree of an unknown pointer %p\n", p);
     std::abort();
   }
+  call_log("hipFree %zu", it->second);
   std::memset(p, 0x5A, it->second);
   g_used -= it->second;
   g_allocs.erase(it);
   free(p);
   return hipSuccess;
 }
-hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind k) {
+  call_log("hipMemcpy %zu kind %d", bytes, (int)k);
   if (bytes) std::memmove(dst, src, bytes);
   return hipSuccess;
 }
@@ -402,19 +422,24 @@ static std::atomic<int> g_h2d_async{0};
 extern "C" int hostsim_h2d_async_copies() { return g_h2d_async.load(); }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind k, hipStream_t) {
   if (k == hipMemcpyHostToDevice) ++g_h2d_async;
-  return hipMemcpy(dst, src, bytes, k);
+  call_log("hipMemcpyAsync %zu kind %d", bytes, (int)k);
+  if (bytes) std::memmove(dst, src, bytes);
+  return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t) {
+  call_log("hipMemset %zu value %d", bytes, value);
   if (bytes) std::memset(dst, value, bytes);
   return hipSuccess;
 }
 hipError_t hipMemset(void* dst, int value, size_t bytes) { return hipMemsetAsync(dst, value, bytes, nullptr); }
 hipError_t hipMemGetInfo(size_t* free_b, size_t* total_b) {
+  call_log("hipMemGetInfo free %zu", kTotal - g_used);
   if (free_b) *free_b = kTotal - g_used;
   if (total_b) *total_b = kTotal;
   return hipSuccess;
 }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
+  call_log("hipStreamCreate");
   *s = (hipStream_t) new int(0);
   return hipSuccess;
 }
@@ -422,13 +447,18 @@ hipError_t hipStreamDestroy(hipStream_t s) {
   delete (int*)s;
   return hipSuccess;
 }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) {
+  call_log("hipStreamSynchronize");
+  return hipSuccess;
+}
 hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e) {
+  call_log("hipEventCreate");
   *e = new ihipEvent_t{0.0};
   return hipSuccess;
 }
 hipError_t hipHostMalloc(void** p, size_t bytes, unsigned) {
+  call_log("hipHostMalloc %zu", bytes);
   *p = std::malloc(bytes ? bytes : 1);
   return *p ? hipSuccess : hipErrorOutOfMemory;
 }
@@ -444,11 +474,13 @@ hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCre
 // a launch runs when it is enqueued, so whatever an event stands for has already happened
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t e, unsigned) { return e ? hipSuccess : hipErrorInvalidValue; }
 hipError_t hipEventDestroy(hipEvent_t e) {
+  call_log("hipEventDestroy");
   delete e;
   return hipSuccess;
 }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) {
   if (!e) return hipErrorInvalidValue;
+  call_log("hipEventRecord");
   e->t = now_ms();
   return hipSuccess;
 }

@@ -1308,3 +1308,51 @@ def test_partitioned_plans_are_the_pinned_ones(sim, idx):
     what, args, opts, want = PINNED_PLANS[idx]
     got = {"groupby": _groupby_plan, "idx": _idx_plan, "join": _join_plan, "probe": _probe_report}[what](sim, *args, **opts)
     assert got == want, (what, args, opts, got)
+
+
+# ---- the step executor's stages (api.cpp execute_impl: try_route, the compiled-filter stages, the layout twins, select_family,
+# join_probe_payload, size_scratch, launch_family, finish_step's retries): routes and reports, pinned --------------------------
+from tests import stage_cases  # noqa: E402
+
+
+@pytest.mark.parametrize("idx", range(len(stage_cases.PINNED)))
+def test_executor_stages_are_the_pinned_ones(sim, oracle, idx):
+    """mi355q_explain's (code, route, scratch bytes) and mi355q_execute's report of a few dozen small steps — every stage
+    function of the executor is on the way of at least one — are those of the commit before execute_impl became a list of
+    stage functions; a step of the case matrix that succeeds also gives the oracle's table."""
+    from heavydb_amd.executor import Executor, FetchResult
+    name, layout, opts_name, want_explain, want_report = stage_cases.PINNED[idx]
+    case = stage_cases.with_layout(stage_cases.by_name()[name], layout)
+    opts = stage_cases.OPTS[opts_name]
+    sim.hostsim_configure(flow.ALL_ROUTES, 0, 0, 0)
+    hj, keep = flow._build_join(case)
+    case.ra.join_table = hj
+    try:
+        ex = Executor(0)
+        plan = case.ra.to_plan()
+        rows = [len(f[0]) for f in case.frags]
+        fr0 = FetchResult([[0] * plan.n_cols for _ in rows], rows, [0] * 8 if case.inner else [], len(case.inner[0]) if case.inner else 0)
+        inp, keep_inp = fr0.to_c(plan.n_cols)
+        o = ex._opts(None, None, opts.get("force_generic", False), opts.get("kernel_variant", 0), 0, pass_rows=opts.get("pass_rows", 0),
+                     flags=opts.get("flags", 0))
+        buf, got = C.create_string_buffer(512), C.c_int64()
+        code = sim.mi355q_explain(C.byref(plan), C.byref(inp), C.byref(o), buf, 512, C.byref(got))
+        assert (code, buf.value.decode(), got.value) == tuple(want_explain), (name, layout, opts_name)
+        if want_report[0] != 0:
+            with pytest.raises(capi.Mi355qError) as ei:
+                ex.executeWorkUnit(case.ra, flow._fetch_result(case), allow_retry=False, **opts)
+            assert ei.value.code == want_report[0]
+            return
+    finally:
+        case.ra.join_table = None
+    if stage_cases.held_to_oracle(case, layout):
+        rs = flow._check(oracle, case, **opts)
+    else:
+        case.ra.join_table = hj
+        try:
+            rs = Executor(0).executeWorkUnit(case.ra, flow._fetch_result(case), allow_retry=False, **opts)
+        finally:
+            case.ra.join_table = None
+    r = rs.report
+    assert (0, r.kernel_name.decode(), r.variant, r.n_launches, r.spilled_rows, r.rows_scanned, r.algorithmic_bytes) == tuple(want_report), \
+        (name, layout, opts_name)

@@ -241,6 +241,22 @@ class JoinSpec(C.Structure):
     ]
 
 
+KEYED_ENTRIES_FROM_NDV = -1   # JoinSpec.keyed_entry_count: size a keyed table at 2 x the NDV estimate of its keys
+
+
+class NdvSpec(C.Structure):
+    _fields_ = [
+        ("device_id", C.c_int32),
+        ("n_keys", C.c_int32),
+        ("key_types", C.c_int32 * MAX_GROUP_COLS),
+        ("key_nullables", C.c_int32 * MAX_GROUP_COLS),
+        ("precision_bits", C.c_int32),
+        ("n_frags", C.c_int32),
+        ("key_buffers", C.POINTER(C.c_void_p)),
+        ("frag_rows", C.POINTER(C.c_int64)),
+    ]
+
+
 # every symbol include/mi355q.h declares: (name, restype, argtypes)
 _P = C.POINTER
 SYMBOLS = [
@@ -286,6 +302,7 @@ SYMBOLS = [
     ("mi355q_result_fetch_rows", C.c_int32,
      [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int64)]),
     ("mi355q_result_to_columns", C.c_int32, [C.c_void_p, _P(C.c_void_p), C.c_int32, _P(C.c_int64), C.c_void_p]),
+    ("mi355q_estimate_ndv", C.c_int32, [_P(NdvSpec), C.c_void_p, C.c_void_p, _P(C.c_int64)]),
     ("mi355q_join_build", C.c_int32, [_P(JoinSpec), C.c_void_p, _P(C.c_void_p)]),
     ("mi355q_join_free", None, [C.c_void_p]),
     ("mi355q_join_key_shape", C.c_int32, [C.c_void_p, _P(C.c_int32), _P(C.c_int32)]),

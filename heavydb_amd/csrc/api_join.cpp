@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -113,13 +114,120 @@ bool mq::api::join_probe_payload(mi355q_join_table* jt, const DevPlan& d, const 
   return false;
 }
 
+// ------------------------------------------------------------------------------- NDV estimate
+namespace {
+
+constexpr int kNdvDefaultBits = 11;  // the reference's hll_precision_bits default
+
+// HyperLogLog.h hll_size: the estimate from the registers, in double precision
+int64_t hll_estimate(const uint32_t* regs, int bits) {
+  const int64_t m = (int64_t)1 << bits;
+  const double alpha = m == 16 ? 0.673 : m == 32 ? 0.697 : m == 64 ? 0.709 : 0.7213 / (1.0 + 1.079 / (double)m);
+  double sum = 0.0;
+  int64_t zeros = 0;
+  for (int64_t i = 0; i < m; ++i) {
+    sum += std::ldexp(1.0, -(int)regs[i]);
+    zeros += regs[i] == 0;
+  }
+  double e = alpha * (double)m * (double)m / sum;
+  if (e <= 2.5 * (double)m && zeros > 0) e = (double)m * std::log((double)m / (double)zeros);
+  return (int64_t)e;
+}
+
+// The registers of `n_frags` fragments of key columns (h_cols: host array [n_frags][kc.n] of device pointers; kc's own
+// column pointers are not read) folded into registers_dev, or into zeroed registers of its own, and the estimate of
+// what they then hold.  The arguments have been checked; the device is set.  Waits for the stream.
+int32_t ndv_run(const JoinKeyCols& kc, int bits, int n_frags, const void* const* h_cols, const int64_t* h_rows,
+                uint32_t* registers_dev, int device_id, hipStream_t s, int64_t* ndv) {
+  const size_t reg_bytes = sizeof(uint32_t) << bits;
+  DevWord own, table;
+  uint32_t* regs = registers_dev;
+  if (!regs) {
+    HIP_TRY(hipMalloc(&own.p, reg_bytes));
+    regs = (uint32_t*)own.p;
+    HIP_TRY(hipMemsetAsync(regs, 0, reg_bytes, s));
+  }
+  // the fragments that have rows: column pointers, then row counts, as one table on the device
+  std::vector<int64_t> h_table;
+  std::vector<int64_t> rows;
+  int64_t total = 0;
+  bool vec = true;
+  for (int k = 0; k < kc.n; ++k) vec = vec && (kc.type[k] == MI355Q_INT32 || kc.type[k] == MI355Q_INT64);
+  for (int f = 0; f < n_frags; ++f) {
+    if (h_rows[f] <= 0) continue;
+    for (int k = 0; k < kc.n; ++k) {
+      const uintptr_t ptr = (uintptr_t)h_cols[(size_t)f * kc.n + k];
+      vec = vec && (ptr & 15) == 0;
+      h_table.push_back((int64_t)ptr);
+    }
+    rows.push_back(h_rows[f]);
+    total += h_rows[f];
+  }
+  if (total > 0) {
+    static_assert(sizeof(void*) == sizeof(int64_t), "pointer table and row counts share one array");
+    const size_t n_ptr = h_table.size();
+    h_table.insert(h_table.end(), rows.begin(), rows.end());
+    HIP_TRY(hipMalloc(&table.p, h_table.size() * sizeof(int64_t)));
+    HIP_TRY(hipMemcpy(table.p, h_table.data(), h_table.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    NdvArgs a{};
+    a.cols = (const int8_t* const*)table.p;
+    a.rows = (const int64_t*)table.p + n_ptr;
+    a.regs = regs;
+    a.n_frags = (int32_t)rows.size();
+    a.n_keys = kc.n;
+    a.width = kc.width;
+    a.bits = bits;
+    for (int k = 0; k < kc.n; ++k) {
+      a.type[k] = kc.type[k];
+      a.nullable[k] = kc.nullable[k];
+    }
+    a.vec = vec ? 1 : 0;
+    HIP_TRY(launch_ndv_hll(a, total, cu_count_of(device_id), s));
+  }
+  std::vector<uint32_t> h_regs((size_t)1 << bits);
+  HIP_TRY(hipMemcpyAsync(h_regs.data(), regs, reg_bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *ndv = hll_estimate(h_regs.data(), bits);
+  return MI355Q_OK;
+}
+
+}  // namespace
+
 extern "C" {
+
+int32_t mi355q_estimate_ndv(const mi355q_ndv_spec* spec, uint32_t* registers_dev, void* stream, int64_t* ndv) {
+  if (!spec || !ndv) return MI355Q_ERR_INVALID_PLAN;
+  if (spec->n_keys < 1 || spec->n_keys > MI355Q_MAX_GROUP_COLS || spec->n_frags < 0) return MI355Q_ERR_INVALID_PLAN;
+  const int bits = spec->precision_bits == 0 ? kNdvDefaultBits : spec->precision_bits;
+  if (bits < 4 || bits > 13) return MI355Q_ERR_INVALID_PLAN;
+  if (spec->n_frags > 0 && !spec->frag_rows) return MI355Q_ERR_INVALID_PLAN;
+  for (int f = 0; f < spec->n_frags; ++f) {
+    if (spec->frag_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
+    if (spec->frag_rows[f] == 0) continue;
+    if (!spec->key_buffers) return MI355Q_ERR_INVALID_PLAN;
+    for (int k = 0; k < spec->n_keys; ++k)
+      if (!spec->key_buffers[(size_t)f * spec->n_keys + k]) return MI355Q_ERR_INVALID_PLAN;
+  }
+  JoinKeyCols kc{};
+  kc.n = spec->n_keys;
+  kc.width = 4;
+  for (int k = 0; k < kc.n; ++k) {
+    kc.type[k] = spec->key_types[k];
+    kc.nullable[k] = spec->key_nullables[k];
+    if (kc.type[k] < MI355Q_INT8 || kc.type[k] > MI355Q_INT64) return MI355Q_ERR_UNSUPPORTED;
+    if (type_width(kc.type[k]) > 4) kc.width = 8;  // BaselineJoinHashTable::getKeyComponentWidth
+  }
+  DeviceGuard g(spec->device_id);
+  if (!g.ok) return MI355Q_ERR_HIP;
+  return ndv_run(kc, bits, spec->n_frags, spec->key_buffers, spec->frag_rows, registers_dev, spec->device_id,
+                 (hipStream_t)stream, ndv);
+}
 
 // ------------------------------------------------------------------------------- joins
 namespace {
 
 // One attempt at one layout.  `one_to_many` selects hash types 2/3 instead of 0/1.
-int32_t join_build_layout(const mi355q_join_spec* spec, bool perfect, bool one_to_many,
+int32_t join_build_layout(const mi355q_join_spec* spec, bool perfect, bool one_to_many, int64_t keyed_entries,
                           const JoinKeyCols& kc, hipStream_t s, mi355q_join_table* jt, int32_t* d_err) {
   const mi355q_range& r = spec->key_range;
   const int64_t n = spec->num_rows;
@@ -144,8 +252,7 @@ int32_t join_build_layout(const mi355q_join_spec* spec, bool perfect, bool one_t
     jt->entry_count = r.max - r.min + 1;
   } else {
     jt->min_key = jt->max_key = 0;
-    jt->entry_count = spec->keyed_entry_count > 0 ? spec->keyed_entry_count
-                                                  : 2 * std::max<int64_t>(n, 1);  // BaselineJoinHashTable.cpp:484
+    jt->entry_count = keyed_entries;
     if (jt->entry_count > (int64_t)UINT32_MAX) return MI355Q_ERR_UNSUPPORTED;
   }
   const int64_t entries = jt->entry_count;
@@ -240,14 +347,31 @@ int32_t mi355q_join_build(const mi355q_join_spec* spec, void* stream, mi355q_joi
     }
   } eg{e0, e1};
   HIP_TRY(hipEventRecord(e0, s));
+  // a keyed table: the caller's entry count, else 2 x rows — or, asked for, 2 x the NDV estimate of the keys, which is
+  // what the reference sizes it at (BaselineJoinHashTable.cpp:484-486)
+  const int64_t default_entries = 2 * std::max<int64_t>(spec->num_rows, 1);
+  int64_t keyed_entries = spec->keyed_entry_count > 0 ? spec->keyed_entry_count : default_entries;
+  const bool from_ndv = !perfect && spec->keyed_entry_count == MI355Q_KEYED_ENTRIES_FROM_NDV;
+  if (from_ndv) {
+    const void* cols[MI355Q_MAX_GROUP_COLS];
+    for (int i = 0; i < n_keys; ++i) cols[i] = kc.col[i];
+    int64_t ndv = 0;
+    if (int32_t e = ndv_run(kc, kNdvDefaultBits, 1, cols, &spec->num_rows, nullptr, spec->device_id, s, &ndv)) return e;
+    keyed_entries = 2 * std::max<int64_t>(ndv, 1);
+  }
   int32_t h_err = 0;
-  // the reference tries OneToOne first and rebuilds as OneToMany when the fill reports a
-  // duplicate key (PerfectJoinHashTable::reify / BaselineJoinHashTable::reify)
-  for (int attempt = spec->one_to_many == 2 ? 1 : 0; attempt < 2; ++attempt) {
-    if (int32_t e = join_build_layout(spec, perfect, attempt == 1, kc, s, jt, (int32_t*)err.p)) return e;
-    HIP_TRY(hipMemcpyAsync(&h_err, err.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h_err != MI355Q_ERR_JOIN_NOT_ONE_TO_ONE || spec->one_to_many == 0) break;
+  for (int sizing = 0; sizing < 2; ++sizing) {
+    // the reference tries OneToOne first and rebuilds as OneToMany when the fill reports a
+    // duplicate key (PerfectJoinHashTable::reify / BaselineJoinHashTable::reify)
+    for (int attempt = spec->one_to_many == 2 ? 1 : 0; attempt < 2; ++attempt) {
+      if (int32_t e = join_build_layout(spec, perfect, attempt == 1, keyed_entries, kc, s, jt, (int32_t*)err.p)) return e;
+      HIP_TRY(hipMemcpyAsync(&h_err, err.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      if (h_err != MI355Q_ERR_JOIN_NOT_ONE_TO_ONE || spec->one_to_many == 0) break;
+    }
+    // an estimate must never turn a buildable table into an error: once more at the size no estimate is behind
+    if (!(from_ndv && h_err == MI355Q_ERR_JOIN_TABLE_FULL && keyed_entries < default_entries)) break;
+    keyed_entries = default_entries;
   }
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipStreamSynchronize(s));

@@ -164,6 +164,40 @@ MQ_HD int pack_join_key(const int64_t* keys, int n_keys, int width, uint32_t* wo
   return 2 * n_keys;
 }
 
+// MurmurHash64A, seed 0, of a join key as pack_join_key lays it out (n_keys little-endian components of `width` bytes):
+// what the reference's NDV estimate hashes a key with (approximate_distinct_tuples_impl, HashJoinRuntime.cpp:554-623).
+// 4-byte components make 8-byte blocks two by two; an odd one is the 4-byte tail.
+MQ_HD uint64_t murmur64a_join_key(const int64_t* keys, int n_keys, int width) {
+  const uint64_t m = 0xc6a4a7935bd1e995ull;
+  const int r = 47;
+  uint64_t h = (uint64_t)(n_keys * width) * m;
+  const int n_blocks = width == 8 ? n_keys : n_keys / 2;
+  for (int i = 0; i < n_blocks; ++i) {
+    uint64_t k = width == 8 ? (uint64_t)keys[i]
+                            : ((uint64_t)(uint32_t)keys[2 * i] | ((uint64_t)(uint32_t)keys[2 * i + 1] << 32));
+    k *= m;
+    k ^= k >> r;
+    k *= m;
+    h ^= k;
+    h *= m;
+  }
+  if (width == 4 && (n_keys & 1)) {
+    h ^= (uint64_t)(uint32_t)keys[n_keys - 1];
+    h *= m;
+  }
+  h ^= h >> r;
+  h *= m;
+  h ^= h >> r;
+  return h;
+}
+// HyperLogLog (HyperLogLog.h get_rank / hll_update): the register a hash falls into at precision `bits` is its top
+// `bits` bits; its rank the position of the first set bit of the rest, at most 64 - bits + 1
+MQ_HD uint32_t hll_rank(uint64_t hash, int bits) {
+  const uint64_t rest = hash << bits;
+  const int zeros = rest ? __builtin_clzll(rest) : 64;
+  return (uint32_t)((zeros < 64 - bits ? zeros : 64 - bits) + 1);
+}
+
 // BASELINE.md section 3 generator: u = splitmix64(seed ^ row * golden)
 MQ_HD uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;

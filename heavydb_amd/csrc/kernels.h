@@ -196,6 +196,17 @@ hipError_t launch_join_one_to_many(const JoinKeyCols& kc, int64_t n, int hash_ty
                                    int64_t entries, int64_t min_key, int64_t max_key, int32_t* offsets,
                                    int32_t* counts, int32_t* payloads, int64_t* tile_scratch,
                                    int32_t* d_err, hipStream_t s);
+// HyperLogLog registers over the key columns of some fragments (k_ndv_hll): what mi355q_estimate_ndv and the
+// NDV-sized keyed join tables read their estimate from
+struct NdvArgs {
+  const int8_t* const* cols;  // DEVICE array [n_frags][n_keys]; fragments without rows are left out by the host
+  const int64_t* rows;        // DEVICE array [n_frags]
+  uint32_t* regs;             // DEVICE uint32[1 << bits], folded INTO with atomicMax
+  int32_t n_frags, n_keys, width, bits;  // width: of a key component as hashed (4 / 8, JoinKeyCols::width)
+  int32_t type[MI355Q_MAX_GROUP_COLS], nullable[MI355Q_MAX_GROUP_COLS];
+  int32_t vec, pad_;          // every column INT32 / INT64 and every chunk 16-byte aligned: 16-byte loads
+};
+hipError_t launch_ndv_hll(const NdvArgs& a, int64_t total_rows, int n_cus, hipStream_t s);
 hipError_t launch_generate(void* dst, int64_t n_rows, int64_t row_offset, int kind,
                            uint64_t seed, int64_t a, int64_t b, int64_t c, double a_f,
                            int null_every, hipStream_t s);

@@ -11,6 +11,7 @@
 #include "kernels.h"
 #include "rowfunc.h"
 #include "expr.h"
+#include "fast_common.h"
 
 namespace mq {
 
@@ -427,6 +428,112 @@ __global__ __launch_bounds__(kBlock) void k_join_fill_ids(JoinKeyCols kc, int64_
     const int64_t slot = one_to_many_slot(kc, hash_type, tab, entries, min_key, max_key, keys);
     if (slot < 0) continue;
     payloads[offsets[slot] + atomicAdd(&counts[slot], 1)] = (int32_t)i;
+  }
+}
+
+// ---- NDV estimate of a table's join keys ------------------------------------------------------
+// HyperLogLog registers over the key columns of some fragments (approximate_distinct_tuples_impl,
+// HashJoinRuntime.cpp:554-623; HyperLogLog.h): per row MurmurHash64A of the key as the table would store it, the
+// register the hash names raised to the hash's rank.  The registers of a workgroup live in LDS: a lane reads its
+// register and issues the LDS atomic only where its rank is larger — after the first few thousand rows of a workgroup
+// nearly none is — and at the end the workgroup folds its non-zero registers into the global ones, one atomicMax each.
+// Rows are reached as the streaming families do (fast_common.h scan_fragments): a workgroup walks tiles of
+// kBlock x kNdvUQ quads, every lane with kNdvUQ 16-byte loads per column in flight.  1- and 2-byte columns and chunks
+// off a 16-byte boundary (a.vec == 0) are decoded row by row instead.
+constexpr int kNdvUQ = 2;
+constexpr int kNdvMaxBits = 13;
+
+template <int NK>
+MQ_D void ndv_update(const NdvArgs& a, uint32_t* s_reg, const int64_t (&keys)[NK]) {
+  bool null_key = false;
+#pragma unroll
+  for (int k = 0; k < NK; ++k) null_key = null_key || (a.nullable[k] && keys[k] == plain_int_null(a.type[k]));
+  if (null_key) return;  // as load_join_key: such a row is not in the table
+  const uint64_t h = a.width == 8 ? murmur64a_join_key(keys, NK, 8) : murmur64a_join_key(keys, NK, 4);
+  const uint32_t idx = (uint32_t)(h >> (64 - a.bits));
+  const uint32_t rank = hll_rank(h, a.bits);
+  if (s_reg[idx] < rank) atomicMax(&s_reg[idx], rank);
+}
+
+// four rows of an INT32 / INT64 column, sign-extended
+MQ_D void ndv_load_quad(const int8_t* base, int type, int64_t quad, fast::Quad<int64_t>& q) {
+  if (type == MI355Q_INT64) {
+    fast::load_quad<int64_t>(base, quad, q);
+  } else {
+    fast::Quad<int32_t> t;
+    fast::load_quad<int32_t>(base, quad, t);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q.v[i] = t.v[i];
+  }
+}
+
+template <int NK>
+__global__ __launch_bounds__(kBlock) void k_ndv_hll(NdvArgs a) {
+  __shared__ uint32_t s_reg[1 << kNdvMaxBits];
+  const int n_reg = 1 << a.bits;
+  for (int i = threadIdx.x; i < n_reg; i += kBlock) s_reg[i] = 0;
+  __syncthreads();
+  const int64_t gtid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t gsize = (int64_t)gridDim.x * kBlock;
+  const int64_t tile_q = (int64_t)kBlock * kNdvUQ;
+  for (int f = 0; f < a.n_frags; ++f) {
+    const int8_t* const* fc = a.cols + (size_t)f * NK;
+    const int64_t n = a.rows[f];
+    int64_t keys[NK];
+    if (!a.vec) {
+      for (int64_t i = gtid; i < n; i += gsize) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) keys[k] = decode_int(fc[k], a.type[k], i);
+        ndv_update<NK>(a, s_reg, keys);
+      }
+      continue;
+    }
+    const int64_t nq = n >> 2;
+    const int64_t n_tiles = nq / tile_q;
+    // (the starting workgroup rotates per fragment: short fragments still spread over the grid)
+    for (int64_t t = (blockIdx.x + (int64_t)f * 7) % gridDim.x; t < n_tiles; t += gridDim.x) {
+      const int64_t q0 = t * tile_q + threadIdx.x;
+      fast::Quad<int64_t> kq[kNdvUQ][NK];
+#pragma unroll
+      for (int k = 0; k < NK; ++k) {
+#pragma unroll
+        for (int u = 0; u < kNdvUQ; ++u) ndv_load_quad(fc[k], a.type[k], q0 + (int64_t)u * kBlock, kq[u][k]);
+      }
+#pragma unroll
+      for (int u = 0; u < kNdvUQ; ++u) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+          for (int k = 0; k < NK; ++k) keys[k] = kq[u][k].v[i];
+          ndv_update<NK>(a, s_reg, keys);
+        }
+      }
+    }
+    // ragged end of the fragment: whole quads past the last full tile, then < 4 rows
+    for (int64_t q = n_tiles * tile_q + gtid; q < nq; q += gsize) {
+      fast::Quad<int64_t> k0[NK];
+#pragma unroll
+      for (int k = 0; k < NK; ++k) ndv_load_quad(fc[k], a.type[k], q, k0[k]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) keys[k] = k0[k].v[i];
+        ndv_update<NK>(a, s_reg, keys);
+      }
+    }
+    const int64_t tail = (nq << 2) + gtid;
+    if (tail < n) {
+#pragma unroll
+      for (int k = 0; k < NK; ++k) keys[k] = decode_int(fc[k], a.type[k], tail);
+      ndv_update<NK>(a, s_reg, keys);
+    }
+  }
+  __syncthreads();
+  // (the plain read may be behind the atomics of other workgroups: registers only grow, so a stale value only costs
+  // an atomic that changes nothing)
+  for (int i = threadIdx.x; i < n_reg; i += kBlock) {
+    const uint32_t v = s_reg[i];
+    if (v && a.regs[i] < v) atomicMax(&a.regs[i], v);
   }
 }
 
@@ -1486,6 +1593,23 @@ hipError_t launch_join_one_to_many(const JoinKeyCols& kc, int64_t n, int hash_ty
   if (n > 0) {
     hipLaunchKernelGGL(k_join_fill_ids, dim3(grid_for(n)), dim3(kBlock), 0, s, kc, n, hash_type, tab, entries,
                        min_key, max_key, offsets, counts, payloads);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_ndv_hll(const NdvArgs& a, int64_t total_rows, int n_cus, hipStream_t s) {
+  if (total_rows <= 0 || a.n_frags <= 0) return hipSuccess;
+  if (a.bits < 4 || a.bits > kNdvMaxBits) return hipErrorInvalidValue;
+  // four workgroups per CU: 16 waves to cover the 64-bit multiplies of the hash, 4 x 32 KB of LDS
+  const int64_t tile_rows = (int64_t)kBlock * kNdvUQ * 4;
+  int64_t grid = (total_rows + tile_rows - 1) / tile_rows;
+  if (grid > (int64_t)n_cus * 4) grid = (int64_t)n_cus * 4;
+  switch (a.n_keys) {
+    case 1: hipLaunchKernelGGL(k_ndv_hll<1>, dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(k_ndv_hll<2>, dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+    case 3: hipLaunchKernelGGL(k_ndv_hll<3>, dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+    case 4: hipLaunchKernelGGL(k_ndv_hll<4>, dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

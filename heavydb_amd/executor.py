@@ -361,7 +361,8 @@ class HashJoin:
                     max_perfect_entries: int = 0, stream: int | None = None,
                     one_to_many: int = 0, keyed_entry_count: int = 0) -> "HashJoin":
         """key_buffer / key_type / key_nullable: scalars for one key column, equal-length lists
-        for a composite key."""
+        for a composite key.  keyed_entry_count: entries of a keyed table; 0 = 2 x num_rows,
+        capi.KEYED_ENTRIES_FROM_NDV = 2 x the library's NDV estimate of the keys (estimate_ndv)."""
         lib = capi.load_library()
         bufs = list(key_buffer) if isinstance(key_buffer, (list, tuple)) else [key_buffer]
         types = list(key_type) if isinstance(key_type, (list, tuple)) else [key_type]
@@ -402,6 +403,39 @@ class HashJoin:
             self.free()
         except Exception:
             pass
+
+
+def estimate_ndv(key_cols_per_fragment: Sequence[Sequence[int]], types: Sequence[int], nullables: Sequence[bool],
+                 precision_bits: int = 0, registers: Optional[int] = None, device_id: int = 0,
+                 stream: int | None = None) -> int:
+    """HyperLogLog estimate of the distinct keys of a table (the reference's approximate_distinct_tuples), on the
+    device.  key_cols_per_fragment: per fragment a pair (device addresses of its key columns, rows); types /
+    nullables: per key column; precision_bits: 0 = 11, else 4..13; registers: None, or the device address of
+    uint32[1 << precision_bits] that the call folds INTO — several inputs, or registers of other ranks merged with an
+    element-wise max, accumulate, and the estimate returned is that of everything the registers then hold."""
+    lib = capi.load_library()
+    n_keys = len(types)
+    assert 1 <= n_keys <= capi.MAX_GROUP_COLS and len(nullables) == n_keys
+    n_frags = len(key_cols_per_fragment)
+    flat = (C.c_void_p * max(1, n_frags * n_keys))()
+    rows = (C.c_int64 * max(1, n_frags))()
+    for f, (cols, n) in enumerate(key_cols_per_fragment):
+        if len(cols) != n_keys:
+            raise ValueError("fragment key column count mismatch")
+        for k, ptr in enumerate(cols):
+            flat[f * n_keys + k] = ptr
+        rows[f] = n
+    spec = capi.NdvSpec(device_id, n_keys)
+    for k in range(n_keys):
+        spec.key_types[k] = types[k]
+        spec.key_nullables[k] = int(nullables[k])
+    spec.precision_bits = precision_bits
+    spec.n_frags = n_frags
+    spec.key_buffers = C.cast(flat, C.POINTER(C.c_void_p))
+    spec.frag_rows = C.cast(rows, C.POINTER(C.c_int64))
+    ndv = C.c_int64()
+    check(lib.mi355q_estimate_ndv(C.byref(spec), registers, stream, C.byref(ndv)), "estimate_ndv")
+    return ndv.value
 
 
 def rows_to_arrow(q: capi.QMD, ival: np.ndarray, dval: np.ndarray, is_null: np.ndarray,

@@ -749,8 +749,41 @@ typedef struct mi355q_join_spec {
   int64_t keyed_entry_count; /* 0 = 2 x num_rows; the reference sizes keyed tables at 2 x its
                                 (HyperLogLog) estimate of the distinct keys,
                                 BaselineJoinHashTable.cpp:484-486 — a binding that has that
-                                estimate passes 2 x NDV here */
+                                estimate passes 2 x NDV here;
+                                MI355Q_KEYED_ENTRIES_FROM_NDV: the build runs mi355q_estimate_ndv
+                                over the key columns itself (see below) */
 } mi355q_join_spec;
+
+/* ---- NDV estimate: the reference's HyperLogLog count of the distinct join keys of a table
+ * (approximate_distinct_tuples, HashJoinRuntime.cpp:554-623; HyperLogLog.h).  Per row the key is laid out as a keyed
+ * table stores it (sign-extended components, all 4 bytes wide unless a column is wider than 4 bytes, then all 8;
+ * little-endian, in key order) and hashed with MurmurHash64A, seed 0; rows with a NULL in a nullable component are
+ * skipped, as the fill skips them.  With b = precision_bits and M = 2^b registers: index = hash >> (64 - b),
+ * rank = min(64 - b, leading zeros of hash << b) + 1, register[index] = max(register[index], rank).  The estimate is
+ * computed on the host from the registers: E = alpha M^2 / sum 2^-register, linear counting M ln(M / zeros) where
+ * E <= 2.5 M and a register is zero, no large-range correction; *ndv = (int64)E. */
+typedef struct mi355q_ndv_spec {
+  int32_t device_id;
+  int32_t n_keys;                                  /* 1..MI355Q_MAX_GROUP_COLS */
+  int32_t key_types[MI355Q_MAX_GROUP_COLS];        /* MI355Q_INT8..MI355Q_INT64 */
+  int32_t key_nullables[MI355Q_MAX_GROUP_COLS];
+  int32_t precision_bits;                          /* 0 = 11 (the reference's default); 4..13 */
+  int32_t n_frags;
+  const void* const* key_buffers;                  /* host array [n_frags][n_keys] of device pointers */
+  const int64_t* frag_rows;                        /* host array [n_frags] */
+} mi355q_ndv_spec;
+
+/* registers_dev: NULL, or device uint32_t[1 << precision_bits] that is folded INTO (not cleared): calls over several
+ * inputs, or registers received from other ranks and max-merged by the caller, accumulate (the reference's
+ * hll_unify); *ndv is the estimate of what the registers hold after this call.  The same estimate serves
+ * mi355q_plan.max_groups_buffer_entry_guess (2 x NDV of the group key) for a caller that wants it; the library does
+ * not run it for a GROUP BY on its own.  Returns when the estimate is on the host. */
+int32_t mi355q_estimate_ndv(const mi355q_ndv_spec* spec, uint32_t* registers_dev, void* stream, int64_t* ndv);
+
+/* mi355q_join_spec.keyed_entry_count: a keyed table gets 2 x max(NDV estimate at precision 11, 1) entries, the
+ * reference's size.  Should a fill then find the table full (an estimate far below the truth), the table is built
+ * once more at the default 2 x num_rows.  Perfect tables ignore the field; build_ms includes the estimate. */
+#define MI355Q_KEYED_ENTRIES_FROM_NDV (-1)
 
 /* HashType / layout of the buffer (docs/source/execution/hash_joins.rst "Hash Join Buffers"):
  *   0 OneToOne perfect   int32 slot[max-min+1], -1 empty (HashJoinRuntime.cpp:71-86)

@@ -112,6 +112,17 @@ def main():
                 ra, fr, 16, {"build_ms_incl_retry": build_ms, "table": hj.info()["hash_type"],
                              "table_bytes": hj.info()["bytes"]})
         hj.free()
+    # the keyed one-to-many table once more, sized by the library's NDV estimate of the keys (2 x ~10 M entries, not 2 x 20 M rows)
+    t0 = time.perf_counter()
+    hj = HashJoin.getInstance(int(dk.data_ptr()), m, INT64, R(True, 0, m // 2 - 1), prefer_baseline=True, one_to_many=1,
+                              keyed_entry_count=capi.KEYED_ENTRIES_FROM_NDV)
+    build_ms = (time.perf_counter() - t0) * 1e3
+    ra = RelAlgExecutionUnit(d, [TargetExpr(COUNT), TargetExpr(SUM, 1), TargetExpr(SUM, 1, 1)],
+                             inner_col_descs=inner, join_outer_col=0, join_table=hj, join_kind=capi.JOIN_INNER)
+    run("f2 INNER join, one-to-many keyed table sized by the NDV estimate (20 M inner rows, 2 per key), COUNT + SUM(fact) + SUM(dim)",
+        ra, fr, 16, {"build_ms_incl_retry": build_ms, "build_ms": hj.info()["build_ms"], "table": hj.info()["hash_type"],
+                     "entry_count": hj.info()["entry_count"], "table_bytes": hj.info()["bytes"]})
+    hj.free()
     # composite key (int64, int64): dim 10 M distinct pairs, one-to-one
     da = torch.arange(10_000_000, device="cuda", dtype=torch.int64)
     db = da % 7

@@ -845,6 +845,11 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
     if (MI355Q_QUAL_OR_GROUP(plan->quals[i].op) != 0) o.force_generic = 1;  // a disjunction among the quals: the row kernel
   set_step_knobs(o);
   const bool async = pend != nullptr;
+  if (async) {
+    TuneKnobs k = tune_knobs();
+    k.async_step = true;
+    set_tune_knobs(k);
+  }
   int32_t e = MI355Q_OK;  // (what the stage or route just asked answered)
 
   // ---- steps with expressions

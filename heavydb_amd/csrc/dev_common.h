@@ -331,6 +331,10 @@ struct DevPlan {
   // the step's filter is NOT in quals[] (n_quals = 0) but a BoolFilter compiled at plan time (boolfilter.h), handed to the
   // kernel beside the plan: only families that take one may run the step
   int32_t bf_active;
+  // baseline layout over ONE plain BIGINT key column whose ExpressionRange is valid and says "no NULLs": the range (a HINT —
+  // the partitioned GROUP BY's lattice member verifies every row against it, kernels_part.hip)
+  int32_t key_rng;
+  int64_t key_rng_min, key_rng_max;
   const int8_t* inner_cols[MI355Q_MAX_COLS];
 };
 

@@ -40,6 +40,7 @@ struct TuneKnobs {
   int64_t pass_rows = 0;
   uint32_t flags = 0;  // MI355Q_OPT_*
   int overlap_cus = 0;  // partitioned GROUP BY: CUs of phase 1 while phase 2 of the previous chunk runs on the rest
+  bool async_step = false;  // mi355q_execute_async: the launches must not wait for the device (no member that reads a word back)
 };
 // n 32-bit words of device memory into host memory the device can address (hipHostGetDevicePointer), one wave
 hipError_t launch_words_to_host(const int32_t* d_src, int32_t* h_dst_dev, int n, hipStream_t s);

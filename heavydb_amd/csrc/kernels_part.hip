@@ -237,8 +237,36 @@ struct ScatterArgs {
   int32_t n_cand;       // heavy-hitter candidate slots (power of two)
   int32_t val_nullable;
   int64_t null_bits;
-  int64_t kmin;         // DIRECT partitioning (join probes): partition = (key - kmin) / S1
+  int64_t kmin;         // DIRECT partitioning (join probes): partition = (key - kmin) / S1; LATTICE: the first lattice point
+  // LATTICE (MODE 3): key = kmin + lat_stride x idx with idx < lat_card; lat_rcp = floor(2^64 / lat_stride) (lat_stride >= 2)
+  uint64_t lat_stride, lat_rcp, lat_card;
 };
+
+// idx = (key - kmin) / stride through the plan-time reciprocal: mulhi(d, floor(2^64 / s)) is floor(d / s) or one less
+// (d / s - d x floor(2^64 / s) / 2^64 < d / 2^64 < 1 — the argument of HomeMap), so one conditional step makes quotient and
+// remainder exact.  true = the key is a lattice point of the range: remainder 0 and idx < card (a key below kmin wraps to
+// a d beyond the range, so its idx is >= card as well).
+MQ_D uint64_t mulhi_u64(uint64_t a, uint64_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(a, b);
+#else
+  return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+MQ_D bool lattice_index(const ScatterArgs& g, int64_t key, uint64_t* idx) {
+  const uint64_t d = (uint64_t)key - (uint64_t)g.kmin;
+  uint64_t q = d, r = 0;
+  if (g.lat_stride > 1) {
+    q = mulhi_u64(d, g.lat_rcp);
+    r = d - q * g.lat_stride;
+    if (r >= g.lat_stride) {
+      r -= g.lat_stride;
+      ++q;
+    }
+  }
+  *idx = q;
+  return r == 0 && q < g.lat_card;
+}
 
 template <typename FT, typename VT>
 struct Tile {
@@ -414,13 +442,18 @@ MQ_D void hot_apply(int op, int64_t* s, int64_t vb, bool is_null) {
 // MODE 1 (DIRECT): by key range, `(key - kmin) / S1`, keys outside [kmin, kmin + hm.d) are dropped —
 // the partitions of a radix join probe (k_part_join / k_part_probe), whose slices then fit LDS / L2;
 // MODE 2: by the home slot of a KEYED join table, MurmurHash1(key) % entries (baseline_hash_join_idx,
-// JoinHashTableQueryRuntime.cpp:56-94), records carry the key (k_part_probe_keyed).
+// JoinHashTableQueryRuntime.cpp:56-94), records carry the key (k_part_probe_keyed);
+// MODE 3 (LATTICE): GROUP BY keys on a lattice kmin + stride x idx: records carry idx, partition = idx mod P (interleaved,
+// so a clustered key range still fills every partition evenly — the run sizing counts on balanced partitions, which a hash
+// gives for free); a key off the lattice raises d_err[2] and is dropped: the caller gives the member up
+// (k_part_aggregate_idx).  The heavy-hitter table and the spill list stay on the real key.
 template <typename FT, typename VT, int MODE = 0>
 __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
     const int8_t* const* __restrict__ cols, const int64_t* __restrict__ num_rows, int n_frags,
     int n_cols, RangeFilter flt, int kcol, int vcol, ScatterArgs g, Rec* __restrict__ scratch,
     uint32_t* __restrict__ cnt, SpillList sl) {
   constexpr bool DIRECT = MODE == 1;
+  constexpr bool LATTICE = MODE == 3;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   Rec* stage = (Rec*)smem_raw;                                      // [P][L] = kStageRecs records
   uint32_t* cursor = (uint32_t*)(smem_raw + kStageRecs * sizeof(Rec));  // [P]
@@ -546,9 +579,19 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
               }
             }
           }
-          if (!folded) {
-            p = part_of(g.hm, DIRECT ? (uint32_t)((uint64_t)key - (uint64_t)g.kmin) : home_from_hash(g.hm, h));
-            rk = MODE != 0 ? key : kid_of(key, h);
+          bool on_lattice = true;
+          if (LATTICE && !folded) {
+            uint64_t idx;
+            on_lattice = lattice_index(g, key, &idx);
+            if (!on_lattice) atomicExch(sl.d_err + 2, 1);
+            p = (uint32_t)idx & (uint32_t)(g.P - 1);
+            rk = (int64_t)idx;
+          }
+          if (!folded && on_lattice) {
+            if (!LATTICE) {
+              p = part_of(g.hm, DIRECT ? (uint32_t)((uint64_t)key - (uint64_t)g.kmin) : home_from_hash(g.hm, h));
+              rk = MODE != 0 ? key : kid_of(key, h);
+            }
             // (the one key whose kid is the LDS tables' empty mark takes the spill list, like a record
             // that meets a full run)
             s = (MODE == 0 && rk == kEmptyKey64) ? g.cap : atomicAdd(&cursor[p], 1u);
@@ -1208,6 +1251,114 @@ __global__ __launch_bounds__(256) void k_spill_merge(PartSlots ps, TableArgs tab
       merge_partial_global(ps, tab, sl, key, part);
     }
     __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------- phase 2, lattice keys
+// Keys on a lattice kmin + stride x idx (k_part_scatter MODE 3: the records carry idx, partition = idx mod P): a unit's
+// groups are addressed directly, e = idx / P, so the LDS table stores NO key — {count 4, other slots 8} per entry — and
+// one unit holds a whole partition (10 M groups, COUNT + SUM(f64): 9 766 entries x 12 B = 117 KB where the keyed table
+// needed two sub-ranges, i.e. a second read of every record).  No probe, no CAS, no twin fold, no bitmap, and nothing
+// waits: every loop is bounded by a count read before it.  A unit's partials are added into its rows of the step's
+// accumulator (`acc`: ns_int 8-byte partials per lattice point, row p x E + e, zeroed at the start of the step; counts
+// widen to 64 bits there; COUNT(*) == 0 marks a point no row has reached).  One workgroup owns a unit and the chunks'
+// launches follow each other on the stream, so those rows are updated with plain loads and stores.
+MQ_D int64_t fold_partial(int op, int64_t a, int64_t b) {
+  switch (op) {
+    case SO_COUNT:
+    case SO_COUNT_NN:
+    case SO_SUM_I: return (int64_t)((uint64_t)a + (uint64_t)b);
+    case SO_SUM_F: return dbl_bits(bits_dbl(a) + bits_dbl(b));
+    case SO_MIN_I: return b < a ? b : a;
+    case SO_MAX_I: return b > a ? b : a;
+    case SO_MIN_F: return bits_dbl(b) < bits_dbl(a) ? b : a;
+    case SO_MAX_F: return bits_dbl(b) > bits_dbl(a) ? b : a;
+    default: return a;
+  }
+}
+MQ_D int count_slot_of(const PartSlots& ps, int ns) {
+  int cs = 0;
+  for (int m = 0; m < ns; ++m)
+    if (ps.int_op[m] == SO_COUNT) cs = m;
+  return cs;
+}
+
+// g: P, B, cap of the scatter; E = entries per unit (multiple of 4), slot_off / lds_table_bytes of the keyless table
+template <int MASK>
+__global__ __launch_bounds__(kPartBlock) void k_part_aggregate_idx(PartGeom g, const Rec* __restrict__ scratch,
+                                                                    const uint32_t* __restrict__ cnt, PartSlots ps,
+                                                                    int64_t* __restrict__ acc) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  uint32_t* lcnt = (uint32_t*)(smem_raw + g.lds_table_bytes);  // [B]
+  const int ns = g.ns_int;
+  const int t = threadIdx.x;
+  const int lgP = 31 - __builtin_clz((uint32_t)g.P);
+  const int cs = count_slot_of(ps, ns);
+  for (int p = blockIdx.x; p < g.P; p += gridDim.x) {
+    for (uint32_t e = t; e < g.E; e += kPartBlock) {
+      for (int m = 0; m < ns; ++m) {
+        if (is_count_op(ps.int_op[m])) ((uint32_t*)(smem_raw + g.slot_off[m]))[e] = 0;
+        else ((int64_t*)(smem_raw + g.slot_off[m]))[e] = ps.int_init[m];
+      }
+    }
+    for (int b = t; b < g.B; b += kPartBlock) lcnt[b] = cnt[(size_t)p * g.B + b];
+    __syncthreads();
+    // one wave per run; four 16-byte record loads per lane, the next four already in flight
+    const int wave = t >> 6, lane = t & 63;
+    for (int b = wave; b < g.B; b += kPartBlock / 64) {
+      uint32_t n = lcnt[b];
+      if (n > g.cap) n = g.cap;
+      if (!n) continue;
+      const Rec* run = scratch + ((size_t)p * g.B + b) * g.cap;
+      const uint32_t last = n - 1;
+      auto at = [&](uint32_t i) -> uint32_t { return i < last ? i : last; };  // clamped: always loadable
+      auto one = [&](const Rec& r, bool valid) {
+        const uint64_t e = (uint64_t)r.key >> lgP;
+        if (valid && e < g.E) apply_row<MASK>(smem_raw, g, ps, (uint32_t)e, r.val);
+      };
+      Rec c0 = run[at(lane)], c1 = run[at(lane + 64)], c2 = run[at(lane + 128)], c3 = run[at(lane + 192)];
+      for (uint32_t base = 0; base < n; base += 256) {
+        const uint32_t i = base + lane, nx = i + 256;
+        const Rec n0 = run[at(nx)], n1 = run[at(nx + 64)], n2 = run[at(nx + 128)], n3 = run[at(nx + 192)];
+        one(c0, i < n);
+        one(c1, i + 64 < n);
+        one(c2, i + 128 < n);
+        one(c3, i + 192 < n);
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+      }
+    }
+    __syncthreads();
+    for (uint32_t e = t; e < g.E; e += kPartBlock) {
+      if (((const uint32_t*)(smem_raw + g.slot_off[cs]))[e] == 0) continue;
+      int64_t* row = acc + ((size_t)p * g.E + e) * ns;
+      const bool fresh = row[cs] == 0;  // no earlier chunk has reached this point: its row is still the zeroes
+      for (int m = 0; m < ns; ++m) {
+        const int64_t v = lds_slot_value(ps.int_op[m], smem_raw + g.slot_off[m], e);
+        row[m] = fresh ? v : fold_partial(ps.int_op[m], row[m], v);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// after the last chunk: every point some row has reached leaves for the output table under its real key, through the
+// reference's insert-or-find — a row the heavy-hitter / full-run spill path of an earlier chunk created is merged into
+__global__ __launch_bounds__(256) void k_lattice_emit(PartGeom g, PartSlots ps, TableArgs tab, SpillList sl,
+                                                      const int64_t* __restrict__ acc, int64_t kmin, uint64_t stride,
+                                                      uint64_t card) {
+  const int ns = g.ns_int;
+  const int lgP = 31 - __builtin_clz((uint32_t)g.P);
+  const int cs = count_slot_of(ps, ns);
+  const uint64_t n = (uint64_t)g.P * g.E;
+  for (uint64_t a = (uint64_t)blockIdx.x * 256 + threadIdx.x; a < n; a += (uint64_t)gridDim.x * 256) {
+    const int64_t* row = acc + a * ns;
+    if (row[cs] == 0) continue;
+    const uint64_t p = a / g.E, e = a - p * g.E;
+    const uint64_t idx = (e << lgP) | p;
+    if (idx >= card) continue;
+    int64_t part[kMaxInt];
+    for (int m = 0; m < kMaxInt; ++m) part[m] = m < ns ? row[m] : 0;
+    merge_partial_global(ps, tab, sl, (int64_t)((uint64_t)kmin + idx * stride), part);
   }
 }
 
@@ -2352,27 +2503,28 @@ hipError_t launch_scatter_t(int grid, size_t lds, hipStream_t s, const FragView&
   return hipGetLastError();
 }
 
-template <typename FT>
+template <typename FT, int MODE>
 hipError_t launch_scatter_v(const FastShape& fs, int grid, size_t lds, hipStream_t s,
                             const FragView& fv, const Chunk& c, int kcol, const ScatterArgs& g,
                             const ScratchCarve& b, const SpillList& sl) {
   const int vcol = fs.vcol < 0 ? 0 : fs.vcol;
   if (fs.vcol < 0)
-    return launch_scatter_t<FT, none_t, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
+    return launch_scatter_t<FT, none_t, MODE>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
   if (fs.vtype == MI355Q_INT64)
-    return launch_scatter_t<FT, int64_t, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
+    return launch_scatter_t<FT, int64_t, MODE>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
   if (fs.vtype == MI355Q_INT32)
-    return launch_scatter_t<FT, int32_t, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
-  return launch_scatter_t<FT, double, 0>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
+    return launch_scatter_t<FT, int32_t, MODE>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
+  return launch_scatter_t<FT, double, MODE>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
 }
 
-// GROUP BY: the member for the filter column's type and the value column's
+// GROUP BY (MODE 0 hashed records, 3 lattice indices): the member for the filter column's type and the value column's
+template <int MODE>
 hipError_t launch_scatter(const FastShape& fs, int grid, size_t lds, hipStream_t s, const FragView& fv, const Chunk& c,
                           int kcol, const ScatterArgs& g, const ScratchCarve& b, const SpillList& sl) {
-  if (fs.fil_type == 0) return launch_scatter_v<none_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
-  if (fs.fil_type == MI355Q_INT32) return launch_scatter_v<int32_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
-  if (fs.fil_type == MI355Q_INT8) return launch_scatter_v<int8_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
-  return launch_scatter_v<int64_t>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+  if (fs.fil_type == 0) return launch_scatter_v<none_t, MODE>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+  if (fs.fil_type == MI355Q_INT32) return launch_scatter_v<int32_t, MODE>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+  if (fs.fil_type == MI355Q_INT8) return launch_scatter_v<int8_t, MODE>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
+  return launch_scatter_v<int64_t, MODE>(fs, grid, lds, s, fv, c, kcol, g, b, sl);
 }
 
 // join probes (MODE 1 DIRECT, 2 keyed): no filter, an int64 value column (`vcol` >= 0) or none
@@ -2394,6 +2546,51 @@ TableArgs make_table_args(const DevPlan& p, const FastShape& fs, int64_t* out) {
   return tab;
 }
 
+// ---- the lattice member (k_part_scatter MODE 3 + k_part_aggregate_idx + k_lattice_emit): host side
+// Its working memory lies behind the exchange buffers in the scratch: the words of the stride sample (launch_key_gcd),
+// then the accumulator, sized for the most lattice points the plan's units can hold in LDS — the stride, and with it the
+// number of points, is only known once the step runs.  bytes == 0: the plan is no candidate and reserves nothing.
+bool count_op_host(int op) { return op == SO_COUNT || op == SO_COUNT_NN; }
+constexpr int64_t kGcdScratchWords = 64 * 256, kGcdOutWords = 256;
+struct LatticeArea {
+  int64_t off, bytes;
+  size_t entry_bytes;   // of the keyless LDS table: 4 per count slot, 8 per other slot
+  uint32_t e_fit;       // entries of that table within kLdsTableBudget
+};
+LatticeArea lattice_area(const DevPlan& p, const PartPlanHost& h) {
+  LatticeArea a{};
+  const TuneKnobs& k = tune_knobs();
+  // (an asynchronous step must not wait for the stride; the overlapped pipeline keeps its own member)
+  if ((k.flags & MI355Q_OPT_NO_LATTICE_PART) || k.async_step || h.overlap) return a;
+  // one plain BIGINT key column whose range is known and holds no NULL; INT64_MAX is the table's empty mark
+  if (!p.key_rng || p.group_type != MI355Q_INT64 || p.key_rng_max == INT64_MAX) return a;
+  if (!(h.op_mask & (1 << SO_COUNT))) return a;  // COUNT(*) is how emission knows that a group exists
+  for (int m = 0; m < h.g.ns_int; ++m) a.entry_bytes += count_op_host(h.ps.int_op[m]) ? 4 : 8;
+  a.e_fit = (uint32_t)(kLdsTableBudget / a.entry_bytes);
+  a.off = (h.scratch_bytes + 64 + 255) & ~255ll;
+  a.bytes = (kGcdScratchWords + kGcdOutWords) * 8 + (int64_t)h.g.P * ((a.e_fit + 3) & ~3u) * h.g.ns_int * 8;
+  return a;
+}
+
+using AggIdxKernel = decltype(&k_part_aggregate_idx<0>);
+AggIdxKernel aggregate_idx_member(int op_mask, size_t lds2) {
+  AggIdxKernel k = k_part_aggregate_idx<0>;
+  switch (op_mask) {
+    case 1 << SO_COUNT: k = k_part_aggregate_idx<(1 << SO_COUNT)>; break;
+    case (1 << SO_COUNT) | (1 << SO_SUM_F): k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_F))>; break;
+    case (1 << SO_COUNT) | (1 << SO_SUM_I): k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_I))>; break;
+    case (1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN):
+      k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN))>;
+      break;
+    case (1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN):
+      k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN))>;
+      break;
+    default: break;
+  }
+  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+  return k;
+}
+
 }  // namespace
 
 bool part_supported(const DevPlan& p, const FragView& fv, int n_cus) {
@@ -2408,7 +2605,8 @@ int64_t part_scratch_bytes(const DevPlan& p, const FragView& fv, int n_cus, int6
   if (!grouped_fast_shape(p, fv, &fs)) return 0;
   PartPlanHost h;
   if (!make_part_plan(p, fs, fv, n_cus, cap_bytes, &h)) return 0;
-  return h.scratch_bytes + 64;
+  const LatticeArea lat = lattice_area(p, h);
+  return lat.bytes ? lat.off + lat.bytes : h.scratch_bytes + 64;
 }
 
 hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int64_t* out,
@@ -2450,8 +2648,121 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
   sa.null_bits = h.ps.null_bits;
   TimedLaunches timed{st, s};
   auto scatter_chunk = [&](const Chunk& c, const ScratchCarve& b) {
-    return timed.run([&] { return launch_scatter(fs, h.g.B, h.lds1, s, fv, c, p.group_col, sa, b, spills(b)); });
+    return timed.run([&] { return launch_scatter<0>(fs, h.g.B, h.lds1, s, fv, c, p.group_col, sa, b, spills(b)); });
   };
+  const bool trace = (opt_flags & MI355Q_OPT_TRACE) != 0;
+  // ---- keys on a lattice: records carry the lattice index, phase 2 reads them once into keyless LDS tables.  The stride
+  // is a sample's (the first <= 4 M rows of the first fragment that has rows; one small kernel and one wait per step) and
+  // every row is verified against it: a key off the lattice gives the member up and the plain member runs below.
+  const LatticeArea lat = lattice_area(p, h);
+  auto lattice_member = [&](bool* done) -> hipError_t {
+    *done = false;
+    int first = -1;
+    for (int f = 0; f < fv.n_frags && first < 0; ++f)
+      if (fv.h_num_rows[f] > 0) first = f;
+    if (first < 0) return hipSuccess;
+    unsigned long long* g_scr = (unsigned long long*)((char*)scratch + lat.off);
+    unsigned long long* g_out = g_scr + kGcdScratchWords;
+    int64_t* acc = (int64_t*)(g_out + kGcdOutWords);
+    const int64_t kmin = p.key_rng_min;
+    hipError_t e2 = launch_key_gcd(fv.h_cols[(size_t)first * fv.n_cols + p.group_col], 8,
+                                   fv.h_num_rows[first] < ((int64_t)4 << 20) ? fv.h_num_rows[first] : ((int64_t)4 << 20), kmin,
+                                   p.group_nullable, g_scr, g_out, s);
+    if (e2 != hipSuccess) return e2;
+    unsigned long long h_g[kGcdOutWords];
+    if ((e2 = hipMemcpyAsync(h_g, g_out, sizeof(h_g), hipMemcpyDeviceToHost, s)) != hipSuccess) return e2;
+    if ((e2 = hipStreamSynchronize(s)) != hipSuccess) return e2;
+    unsigned long long stride = 0;
+    for (int i = 0; i < (int)kGcdOutWords; ++i) {
+      unsigned long long x = h_g[i], y = stride;
+      while (y) {
+        const unsigned long long r = x % y;
+        x = y;
+        y = r;
+      }
+      stride = x;
+    }
+    if (stride == 0) stride = 1;  // (every sampled key is the minimum)
+    const uint64_t card = ((uint64_t)p.key_rng_max - (uint64_t)kmin) / stride + 1;
+    // (card reaches 2^64 - 1 for a range that spans the type: no rounding sum that could wrap)
+    const uint64_t per_unit = card / (uint64_t)h.g.P + (card % (uint64_t)h.g.P ? 1 : 0);
+    if (per_unit > lat.e_fit) {
+      if (trace) std::fprintf(stderr, "[mi355q] phase 2 member: k_part_aggregate (stride %llu: %llu lattice points, a unit's LDS table holds %u of %llu)\n",
+                              stride, (unsigned long long)card, lat.e_fit, (unsigned long long)per_unit);
+      return hipSuccess;
+    }
+    PartGeom lg = h.g;
+    lg.E = ((uint32_t)per_unit + 3) & ~3u;  // keeps every slot array 16-byte aligned
+    {
+      uint32_t off = 0;  // 8-byte slot arrays first, then the 4-byte counters
+      for (int m = 0; m < kMaxInt; ++m) lg.slot_off[m] = 0;
+      for (int m = 0; m < lg.ns_int; ++m)
+        if (!count_op_host(h.ps.int_op[m])) { lg.slot_off[m] = off; off += lg.E * 8; }
+      for (int m = 0; m < lg.ns_int; ++m)
+        if (count_op_host(h.ps.int_op[m])) { lg.slot_off[m] = off; off += lg.E * 4; }
+      lg.lds_table_bytes = off;
+    }
+    const size_t lds2 = (size_t)lg.lds_table_bytes + (size_t)lg.B * 4;
+    const AggIdxKernel agg_idx = aggregate_idx_member(h.op_mask, lds2);
+    ScatterArgs sl3 = sa;
+    sl3.kmin = kmin;
+    sl3.lat_stride = stride;
+    sl3.lat_rcp = stride > 1 ? (uint64_t)((((unsigned __int128)1) << 64) / stride) : 0;
+    sl3.lat_card = card;
+    if (trace) std::fprintf(stderr, "[mi355q] phase 2 member: k_part_aggregate_idx (stride %llu, %llu lattice points, %d units of %u entries)\n",
+                            stride, (unsigned long long)card, lg.P, lg.E);
+    // the table (the spill merges and the emission insert into it) and the accumulator
+    RowInit ri{};
+    ri.row_quad = p.row_quad;
+    for (int k = 0; k < p.key_quad; ++k) ri.quad[k] = kEmptyKey64;
+    for (int j = 0; j < p.slot_count; ++j) ri.quad[p.key_quad + j] = p.init_vals[j];
+    if ((e2 = launch_init_buffer(out, p.entry_count, ri, s)) != hipSuccess) return e2;
+    const size_t acc_bytes = (size_t)lg.P * lg.E * lg.ns_int * 8;
+    if ((e2 = hipMemsetAsync(acc, 0, acc_bytes, s)) != hipSuccess) return e2;
+    (void)hipFuncSetAttribute((const void*)k_spill_merge, hipFuncAttributeMaxDynamicSharedMemorySize, h.g.ns_int * kSpillLds * 8);
+    const SpillList sl0 = spills(b0);
+    for (Chunk c = part_host::next_chunk(fv, 0, h.chunk_rows); c.nf > 0; c = part_host::next_chunk(fv, c.f0 + c.nf, h.chunk_rows)) {
+      e2 = timed.run([&] { return launch_scatter<3>(fs, h.g.B, h.lds1, s, fv, c, p.group_col, sl3, b0, sl0); });
+      if (e2 != hipSuccess) return e2;
+      hipLaunchKernelGGL(agg_idx, dim3(lg.P < h.grid2 ? lg.P : h.grid2), dim3(kPartBlock), lds2, s, lg, (const Rec*)b0.recs, b0.cnt,
+                         h.ps, acc);
+      if ((e2 = hipGetLastError()) != hipSuccess) return e2;
+      hipLaunchKernelGGL(k_spill_merge, dim3(512), dim3(256), (size_t)h.g.ns_int * kSpillLds * 8, s, h.ps, tab, sl0, h.g.ns_int);
+      if ((e2 = hipGetLastError()) != hipSuccess) return e2;
+      if (c.f0 + c.nf < fv.n_frags && (e2 = hipMemsetAsync(b0.spill_base, 0, 4, s)) != hipSuccess) return e2;
+    }
+    {
+      const uint64_t rows = (uint64_t)lg.P * lg.E;
+      const uint64_t want = (rows + 255) / 256, most = (uint64_t)n_cus * 8;
+      hipLaunchKernelGGL(k_lattice_emit, dim3((unsigned)(want < most ? want : most)), dim3(256), 0, s, lg, h.ps, tab, sl0, acc, kmin,
+                         (uint64_t)stride, card);
+      if ((e2 = hipGetLastError()) != hipSuccess) return e2;
+    }
+    int32_t off_lattice = 0;
+    if ((e2 = hipMemcpyAsync(&off_lattice, d_err + 2, sizeof(off_lattice), hipMemcpyDeviceToHost, s)) != hipSuccess) return e2;
+    if ((e2 = hipStreamSynchronize(s)) != hipSuccess) return e2;
+    if (off_lattice) {
+      // nothing is guessed: what the table holds is dropped (the plain member writes every row of it), the error words and
+      // the spill header start over
+      if (trace) std::fprintf(stderr, "[mi355q] lattice member gave up (a key off the lattice of stride %llu): phase 2 member k_part_aggregate\n", stride);
+      if ((e2 = hipMemsetAsync(d_err, 0, 64, s)) != hipSuccess) return e2;
+      if ((e2 = hipMemsetAsync(b0.spill_base, 0, 256, s)) != hipSuccess) return e2;
+      timed.ev_i = 0;
+      st->n_launches = 0;
+      return hipSuccess;
+    }
+    st->spill_counter32 = b0.spill_count();
+    st->n_events_used = timed.ev_i;
+    *done = true;
+    return hipSuccess;
+  };
+  if (lat.bytes && lat.off + lat.bytes <= scratch_bytes) {
+    bool done = false;
+    if ((e = lattice_member(&done)) != hipSuccess) return e;
+    if (done) return hipSuccess;
+  } else if (trace) {
+    std::fprintf(stderr, "[mi355q] phase 2 member: k_part_aggregate\n");
+  }
   if (h.overlap) {
     // ---- phase 1 of chunk i + 1 on g.B CUs next to phase 2 of chunk i on the other grid2 ----
     // stream s: scatter(0), scatter(1), ...  (scatter(i) waits until aggregate(i - 2) has let go of its buffer)

@@ -912,6 +912,16 @@ int32_t build_dev_plan(const mi355q_plan& p, const mi355q_qmd& q, DevPlan* d) {
   d->group_col = grouped ? d->group_cols[0] : -1;
   d->group_type = grouped ? d->group_types[0] : 0;
   d->group_nullable = grouped ? p.cols[p.group_cols[0]].nullable != 0 : 0;
+  if (p.n_group_cols == 1 && q.desc_type == MI355Q_GROUP_BY_BASELINE_HASH) {
+    const mi355q_col_desc& cd = p.cols[p.group_cols[0]];
+    const mi355q_range& r = p.col_ranges[p.group_cols[0]];
+    if (cd.type == MI355Q_INT64 && cd.encoding == MI355Q_ENC_NONE && (cd.logical_type == 0 || cd.logical_type == cd.type) && r.valid &&
+        r.bucket == 0 && r.min <= r.max && !r.has_nulls) {
+      d->key_rng = 1;
+      d->key_rng_min = r.min;
+      d->key_rng_max = r.max;
+    }
+  }
   return MI355Q_OK;
 }
 

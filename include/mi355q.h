@@ -568,6 +568,9 @@ typedef struct mi355q_exec_options {
 #define MI355Q_OPT_NO_IDX_PACK 1024u      /* index-partitioned family: the plain 4 / 8 / 16-byte records even where the value
                                             columns' ranges allow the packed 2- or 4-byte word (tests and tools/refbench.py
                                             compare the two) */
+#define MI355Q_OPT_NO_LATTICE_PART 2048u  /* partitioned GROUP BY: the plain member (hashed records, keyed LDS tables) even where
+                                            the key column is a lattice min + stride x i that the lattice member would
+                                            aggregate by index (tests and bench.py --opt-flags compare the two) */
 
 /* per-call timing/selection report (what launchGpuCode logs,
  * QueryExecutionContext.cpp:334,364,579) */

@@ -208,6 +208,7 @@ OPT_NO_COMPILED_FILTER = 256
 OPT_FILTER_PREPASS = 512
 OPT_NO_IDX_PACK = 1024
 OPT_NO_LATTICE_PART = 2048
+OPT_NO_AGG_PROGRAMS = 4096
 
 
 class ExecReport(C.Structure):

@@ -1268,6 +1268,104 @@ int32_t execute_shifted_args(const mi355q_plan* plan, const mi355q_inputs* in, c
   return MI355Q_OK;
 }
 
+// Non-grouped aggregates whose ARGUMENTS are expressions — SUM(a * b) WHERE c < k, TPC-H Q6's shape.  The reference compiles
+// the argument into the row function (codegenArith, ArithmeticIR.cpp:39-431) and aggregates it in the kernel's registers
+// (query_template, QueryTemplateGenerator.cpp:265-549).  Here every expression that compiles into a two-register program
+// (regprog.h) is evaluated by k_scan_agg_prog on the values the scan has loaded: one kernel, no temporary column, no
+// synchronisation in between (execute_projected: k_project writes 8 bytes per row and expression, k_scan_agg reads them
+// back).  The kernel takes the type and the NULL rule of an argument from the lowered plan's targets — what the plain-column
+// step would have applied to the temporary column — so both paths state the same result.  Taken at every input size: a
+// non-grouped step has no table to amortise.  kNotTaken: anything the form does not state (regprog.h agg_prog_args_of,
+// kernels_filter.hip sap_args); that plan keeps the projection pass.
+int32_t execute_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
+                             mi355q_exec_report* report, int64_t* reserved) {
+  if (plan->n_exprs <= 0 || plan->n_group_cols != 0 || plan->join_outer_col >= 0 || plan->output_columnar_hint != 0 || o.force_generic ||
+      in->n_frags <= 0 || (o.flags & MI355Q_OPT_NO_AGG_PROGRAMS) || plan->n_quals < 0 || plan->n_quals > MI355Q_MAX_QUALS ||
+      plan->n_targets < 1 || plan->n_targets > MI355Q_MAX_TARGETS)
+    return kNotTaken;
+  for (int i = 0; i < plan->n_quals; ++i)
+    if (MI355Q_QUAL_OR_GROUP(plan->quals[i].op) != 0) return kNotTaken;
+  // an expression a qual or another expression reads is evaluated for every row: the projection pass's business
+  if (expr_qual_mask(*plan) != 0 || exprs_read_exprs(*plan)) return kNotTaken;
+  mi355q_plan lp;
+  DevExprSet xs;
+  mi355q_qmd q;
+  DevPlan d;
+  if (lower_exprs(*plan, &lp, &xs, true) != MI355Q_OK || qmd_init(*plan, &q) != MI355Q_OK) return kNotTaken;
+  if (q.desc_type != MI355Q_NON_GROUPED_AGGREGATE || q.slot_width != 8 || q.output_columnar) return kNotTaken;
+  if (build_dev_plan(lp, q, &d) != MI355Q_OK) return kNotTaken;
+  AggProgArgs ap;
+  if (!agg_prog_args_of(d, xs, &ap)) return kNotTaken;
+  const int nf = in->n_frags, nc = plan->n_cols;
+  int64_t total_rows = 0, max_frag_rows = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
+    total_rows += in->num_rows[f];
+    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
+  }
+  // (the kernel reads physical columns only: the table it is handed is the stated one, nc columns per fragment)
+  FragView fv{nullptr, nullptr, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
+  if (!scan_agg_prog_eligible(d, ap, fv)) return kNotTaken;
+  if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched, and there are no temporary columns
+    route_note("aggregate arguments as register programs");
+    route_note("k_scan_agg_prog");
+    *reserved = 0;
+    if (t_plan_only) return MI355Q_OK;
+  }
+  RouteScope rs(in->device_id, o.stream);
+  if (rs.status) return rs.status;
+  DeviceCtx& ctx = rs.ctx;
+  const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
+  // column table | row counts | error words, one upload out of pinned memory (reserve: laid out only)
+  FragTable ft;
+  if (int32_t e = upload_frag_table(ctx, *in, nc, o.stream, reserved ? FragUpload::kNone : FragUpload::kAlways, &ft)) return e;
+  LaunchStats st;
+  if (report || reserved) {
+    while ((int)ctx.events.size() < 4) {
+      hipEvent_t ev;
+      HIP_TRY(hipEventCreate(&ev));
+      ctx.events.push_back(ev);
+    }
+    st.k_start = ctx.events[2];
+    st.k_stop = ctx.events[3];
+  }
+  if (reserved) return MI355Q_OK;
+  hipStream_t s = ft.s;
+  struct UploadGuard {  // the upload reads the SHARED pinned block: no return leaves it in flight
+    hipStream_t s;
+    bool armed;
+    ~UploadGuard() {
+      if (armed) (void)hipStreamSynchronize(s);
+    }
+  } upload_guard{s, true};
+  mi355q_result* res = nullptr;
+  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
+  ResultPtr owned(res);
+  fv.d_cols = ft.d_cols;
+  fv.d_num_rows = ft.d_rows;
+  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
+  HIP_TRY(launch_scan_agg_prog(d, ap, fv, res->buf, ft.d_err, n_cus, s, &st));
+  // the error a passing row raised ends the step with no result, as execute_masked treats its pre-pass's
+  int32_t* h_ret = (int32_t*)(ctx.h_meta + ctx.meta_bytes);
+  HIP_TRY(hipMemcpyAsync(h_ret, ft.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  upload_guard.armed = false;
+  const int32_t code = h_ret[0];
+  if (report) {  // a one-kernel scan step: its event pair is the step's time as well
+    std::memset(report, 0, sizeof(*report));
+    std::snprintf(report->kernel_name, sizeof(report->kernel_name), "%s", st.kernel_name);
+    if (hipEventElapsedTime(&report->kernel_ms, st.k_start, st.k_stop) != hipSuccess) report->kernel_ms = 0.f;
+    report->total_ms = report->kernel_ms;
+    report->n_launches = st.n_launches;
+    report->variant = st.variant;
+    report->rows_scanned = total_rows;
+    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
+  }
+  if (code) return code;
+  *out = owned.release();
+  return MI355Q_OK;
+}
+
 // Plans with projected expressions (mi355q_expr): scan / filter / PROJECT.  The expressions of a pass of
 // fragments are evaluated into dense temporary columns (k_project), the step runs on the lowered plan — where
 // those columns are ordinary inputs, so every kernel family applies — and the passes' results are folded with

@@ -380,6 +380,15 @@ bool filter_mask_eligible(const BoolFilter& bf, const FragView& fv);
 hipError_t launch_filter_mask(const BoolFilter& bf, const BoolFilter* d_bf, const FragView& fv, int8_t* const* d_mask, int32_t* d_err,
                               int n_cus, hipStream_t s);
 
+// non-grouped aggregates whose arguments are two-register programs (regprog.h AggProgArgs: up to 4 arguments over up to 4
+// operand columns) with range quals on up to 4 plain INT32 / INT64 / INT8 columns, evaluated in the scan's registers
+// (kernels_filter.hip k_scan_agg_prog).  `p`: the plan over the lowered columns — its quals, targets and init values.  An
+// error a passing row raises (error 7) goes to d_err[0]; the result is then to be dropped.
+struct AggProgArgs;
+bool scan_agg_prog_eligible(const DevPlan& p, const AggProgArgs& ap, const FragView& fv);
+hipError_t launch_scan_agg_prog(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int64_t* out, int32_t* d_err, int n_cus,
+                                hipStream_t s, LaunchStats* st);
+
 bool join_sum_eligible(const DevPlan& p, const FragView& fv);
 hipError_t launch_join_sum(const DevPlan& p, const FragView& fv, int64_t* out, int n_cus,
                            hipStream_t s, LaunchStats* st);

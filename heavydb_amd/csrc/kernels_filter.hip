@@ -1,5 +1,10 @@
-// kernels_filter.hip — the ROW MASK of a filter compiled at plan time whose atoms include programs (round 6).
+// kernels_filter.hip — the consumers of the two-register programs (regprog.h) that STREAM columns:
+//   k_filter_mask, k_filter_mask_i32   the ROW MASK of a filter compiled at plan time whose atoms include programs (round 6)
+//   k_scan_agg_prog                    non-grouped aggregates whose ARGUMENTS are programs: SUM(a * b) WHERE c < k in one pass
+// (the Projection family evaluates its typed expression targets itself, kernels_proj.hip).  Both run the programs on the
+// four rows of a quad together, on values already in registers, with no stack, no scratch and no node decode per row.
 //
+// ---- the row mask
 // The reference compiles a WHERE clause into the row function (Executor::compileBody, NativeCodegen.cpp:3455; arithmetic
 // leaves: codegenArith / codegenDiv, ArithmeticIR.cpp:39-560; the short-circuit forms behind prioritizeQuals,
 // LogicalIR.cpp:158-297).  Here a filter of comparisons with literals is evaluated INSIDE the consuming kernel (atoms +
@@ -12,9 +17,13 @@
 // interpreter pass of rounds 3-5 wrote and re-read a 4-byte column per expression and ran ~450 wave instructions per 64
 // rows).  An error a row raises (error 7 / error 1) ends the step exactly as the row function's would: every row evaluates
 // the filter's expressions, whatever the plain quals say of it.
+#include <algorithm>
+#include <cstring>
+
 #include "boolfilter.h"
 #include "fast_common.h"
 #include "kernels.h"
+#include "regprog.h"
 
 namespace mq {
 
@@ -387,7 +396,490 @@ __global__ __launch_bounds__(kFmBlock) void k_filter_mask_i32(FilterMaskArgs a) 
   if (err) atomicCAS(a.d_err, 0, err);
 }
 
+// =========================================================================== scan_agg_prog
+// Non-grouped aggregates of EXPRESSIONS — SUM(a * b) WHERE c < k (TPC-H Q6's shape) — in one pass: the scan-aggregate
+// skeleton (kernels_fast.hip k_scan_agg: a workgroup walks contiguous tiles of each fragment, every lane keeps UQ 16-byte
+// non-temporal loads per column in flight, four rows per lane and load, typed register accumulators per argument, a wave
+// shuffle reduce, one LDS fold per workgroup, the partial row merged with reduce_target) with the evaluator of the row
+// mask above: the arguments are two-register programs in LDS (regprog.h AggProgArgs), run on the four rows of a quad
+// together.  The two-pass path (k_project writes an 8-byte column per expression, k_scan_agg reads it back) moves
+// 16 B/row/expression more and synchronises in between.
+// Errors: the row function evaluates a target's expression only for a row that passed the quals, so an error (7: overflow,
+// a narrowing cast) counts only where the quad's pass bit is set — never for a row the quals drop, never for the
+// repeated row behind a fragment's end.  Division is not among the members (rp_eval<.., false>): those plans keep k_project.
+constexpr int kSapFlt = 4;
+struct ScanAggProgArgs {
+  int32_t n_cols, n_args, n_progs, n_frags;
+  int32_t n_shared, n_own, n_cols_table, n_targets;
+  int32_t slot_count, pad_;
+  int32_t col[kApMaxCols], col_w8[kApMaxCols];  // operand slots: index in the column table, 8-byte values (else 4)
+  int32_t arg_slot[kApMaxArgs], arg_type[kApMaxArgs], arg_nullable[kApMaxArgs];
+  int32_t arg_need[kApMaxArgs];                 // 2 = sum, 4 = min, 8 = max (the count of values is always kept)
+  // range quals on an operand column test the values already loaded (sh_slot); the others load their own column
+  RangeFilter sh_flt[kSapFlt], own_flt[kSapFlt];
+  int32_t sh_slot[kSapFlt], own_type[kSapFlt];  // own_type: MI355Q_INT32 / _INT64 / _INT8 (one word per quad)
+  int32_t target_arg[MI355Q_MAX_TARGETS];       // -1 = COUNT(*)
+  DevTarget targets[MI355Q_MAX_TARGETS];
+  int64_t init_vals[MI355Q_MAX_SLOTS];
+  RegProg prog[kApMaxArgs];
+  const int8_t* const* cols;
+  const int64_t* num_rows;
+  int64_t* out;
+  int32_t* d_err;
+};
+static_assert(sizeof(ScanAggProgArgs) <= 3584, "k_scan_agg_prog takes its arguments by value: the kernel argument segment holds 4 KB");
+
+struct SapQuad {
+  v4i32 lo, hi;  // four rows of a column as loaded: lo alone (4-byte values; lo.x alone: 1-byte values), lo + hi (8-byte)
+};
+struct SapAcc {
+  unsigned long long cnt;  // rows that passed with a value that is not NULL
+  int64_t sum, mn, mx;     // by the argument's type: integers, or the bits of a double
+};
+MQ_D int64_t sap_i64(const SapQuad& r, int i) {
+  const v4i32& h = i < 2 ? r.lo : r.hi;
+  const int j = (i & 1) * 2;
+  return (int64_t)(((uint64_t)(uint32_t)fm_v4(h, j + 1) << 32) | (uint64_t)(uint32_t)fm_v4(h, j));
+}
+// four rows loaded one by one (a fragment's last, partial quad) in the registers a 16-byte load would have filled
+MQ_D void sap_pack(const int64_t (&v)[4], int width, SapQuad& r) {
+  if (width == 8) {
+    r.lo.x = (int)(uint32_t)v[0]; r.lo.y = (int)(uint32_t)((uint64_t)v[0] >> 32); r.lo.z = (int)(uint32_t)v[1]; r.lo.w = (int)(uint32_t)((uint64_t)v[1] >> 32);
+    r.hi.x = (int)(uint32_t)v[2]; r.hi.y = (int)(uint32_t)((uint64_t)v[2] >> 32); r.hi.z = (int)(uint32_t)v[3]; r.hi.w = (int)(uint32_t)((uint64_t)v[3] >> 32);
+  } else if (width == 4) {
+    r.lo.x = (int)v[0]; r.lo.y = (int)v[1]; r.lo.z = (int)v[2]; r.lo.w = (int)v[3];
+  } else {
+    r.lo.x = (int)(((uint32_t)v[0] & 255u) | (((uint32_t)v[1] & 255u) << 8) | (((uint32_t)v[2] & 255u) << 16) | (((uint32_t)v[3] & 255u) << 24));
+  }
+}
+MQ_D double sap_wave_sum_f64(double v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+template <bool FP, bool MAX>
+MQ_D int64_t sap_wave_best(int64_t v) {  // MIN / MAX of integers or of doubles held as their bits
+  for (int off = 32; off > 0; off >>= 1) {
+    const int64_t o = (int64_t)__shfl_down((long long)v, off, 64);
+    bool take;
+    if (FP) take = MAX ? bits_dbl(v) < bits_dbl(o) : bits_dbl(o) < bits_dbl(v);
+    else take = MAX ? v < o : o < v;
+    v = take ? o : v;
+  }
+  return v;
+}
+
+// NC / NF: operand columns / filter-only columns this member holds registers for; UQ: quads per column and lane in flight;
+// PF: the next tile's loads are issued before this tile's values are looked at (twice the raw registers).
+// Two workgroups per CU (the grid the scan-aggregate family streams best with): 256 VGPRs per lane, which both members
+// fill — values and programs are 64 bits wide, four rows at a time — without scratch.
+template <int NC, int NF, int UQ, bool PF>
+__global__ __launch_bounds__(kBlock, 2) void k_scan_agg_prog(ScanAggProgArgs a) {
+  __shared__ RegProg s_prog[kApMaxArgs];
+  {
+    const int32_t* src = (const int32_t*)a.prog;
+    int32_t* dst = (int32_t*)s_prog;
+    for (int i = threadIdx.x; i < (int)(sizeof(RegProg) / 4) * a.n_progs; i += kBlock) dst[i] = src[i];
+  }
+  __syncthreads();
+  SapAcc acc[kApMaxArgs];
+#pragma unroll
+  for (int c = 0; c < kApMaxArgs; ++c) {
+    const bool fp = a.arg_type[c] == MI355Q_DOUBLE;
+    acc[c].cnt = 0;
+    acc[c].sum = 0;  // (the bits of 0.0 as well)
+    acc[c].mn = fp ? dbl_bits(1.7976931348623157e308) : INT64_MAX;
+    acc[c].mx = fp ? dbl_bits(-1.7976931348623157e308) : INT64_MIN;
+  }
+  unsigned long long rows_passing = 0;
+  int32_t err = 0;
+  const int tid = threadIdx.x;
+  constexpr int64_t tile_q = (int64_t)kBlock * UQ;
+
+  // one quad of every column: the range quals on the values as loaded (a 4-bit pass mask), the programs on its four rows,
+  // the accumulators.  ONE copy in the kernel: the programs' typed members are inlined four rows wide.
+  auto quad_rows = [&](const SapQuad (&cq)[NC], const SapQuad (&fq)[NF], uint32_t valid) {
+    int64_t vals[4][NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) vals[i][k] = k >= a.n_cols ? 0 : a.col_w8[k] ? sap_i64(cq[k], i) : (int64_t)fm_v4(cq[k].lo, i);
+    }
+    uint32_t pass = valid;
+#pragma unroll
+    for (int k = 0; k < kSapFlt; ++k) {
+      if (k >= a.n_shared) break;
+      const int slot = a.sh_slot[k];
+      uint32_t m = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int64_t x = vals[i][0];
+#pragma unroll
+        for (int c = 1; c < NC; ++c)
+          if (slot == c) x = vals[i][c];
+        m |= (filter_pass<int64_t>(a.sh_flt[k], x) ? 1u : 0u) << i;
+      }
+      pass &= m;
+    }
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+      if (k >= a.n_own) break;
+      const int t = a.own_type[k];
+      uint32_t m = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool p = t == MI355Q_INT32  ? filter_pass<int32_t>(a.own_flt[k], fm_v4(fq[k].lo, i))
+                       : t == MI355Q_INT8 ? filter_pass<int32_t>(a.own_flt[k], (int32_t)(int8_t)((uint32_t)fq[k].lo.x >> (8 * i)))
+                                          : filter_pass<int64_t>(a.own_flt[k], sap_i64(fq[k], i));
+        m |= (p ? 1u : 0u) << i;
+      }
+      pass &= m;
+    }
+    rows_passing += __popc(pass);
+    int64_t av[kApMaxArgs][4];
+#pragma unroll
+    for (int c = 0; c < kApMaxArgs; ++c) {
+      // a plain-column argument: the operand as loaded (wave-uniform selects, never a run-time index into registers)
+      const int slot = c >= a.n_progs && c < a.n_args ? a.arg_slot[c] : 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int64_t x = vals[i][0];
+#pragma unroll
+        for (int k = 1; k < NC; ++k)
+          if (slot == k) x = vals[i][k];
+        av[c][i] = x;
+      }
+    }
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int k = 0; k < a.n_progs; ++k) {
+      int64_t outv[4];
+      int32_t e4[4];
+      rp_eval<4, NC, false>(s_prog[k], vals, outv, e4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (e4[i] && ((pass >> i) & 1u) && !err) err = e4[i];
+#pragma unroll
+      for (int c = 0; c < kApMaxArgs; ++c) {
+        if (k != c) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[c][i] = outv[i];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kApMaxArgs; ++c) {
+      if (c >= a.n_args) break;
+      const int t = a.arg_type[c], need = a.arg_need[c];
+      const bool nul = a.arg_nullable[c] != 0;
+      SapAcc& r = acc[c];
+      if (t == MI355Q_DOUBLE) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const double v = bits_dbl(av[c][i]);
+          const bool ok = ((pass >> i) & 1u) && !(nul && v == kNullDouble);
+          r.cnt += ok ? 1u : 0u;
+          if (need & 2) r.sum = ok ? dbl_bits(bits_dbl(r.sum) + v) : r.sum;
+          if (need & 4) r.mn = (ok && v < bits_dbl(r.mn)) ? av[c][i] : r.mn;
+          if (need & 8) r.mx = (ok && bits_dbl(r.mx) < v) ? av[c][i] : r.mx;
+        }
+      } else {
+        const int64_t null_val = t == MI355Q_INT32 ? (int64_t)INT32_MIN : INT64_MIN;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int64_t x = av[c][i];
+          const bool ok = ((pass >> i) & 1u) && !(nul && x == null_val);
+          r.cnt += ok ? 1u : 0u;
+          if (need & 2) r.sum = (int64_t)((uint64_t)r.sum + (uint64_t)(ok ? x : 0));  // (wraps in 64 bits)
+          if (need & 4) r.mn = (ok && x < r.mn) ? x : r.mn;
+          if (need & 8) r.mx = (ok && r.mx < x) ? x : r.mx;
+        }
+      }
+    }
+  };
+
+  for (int f = 0; f < a.n_frags; ++f) {
+    const int8_t* const* fc = a.cols + (size_t)f * a.n_cols_table;
+    const int64_t n = a.num_rows[f];
+    const int64_t nq = n >> 2;
+    // the fragment's quads, its last partial one included: that one's rows are loaded one by one by the lane it falls to (a
+    // row past the end repeats the last one and is not valid), so the tile loop below is the only path through the fragment
+    const int64_t nq_all = (n + 3) >> 2;
+    const int64_t n_tiles = (nq_all + tile_q - 1) / tile_q;
+    const int8_t *cbase[NC], *fbase[NF];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) cbase[k] = k < a.n_cols ? fc[a.col[k]] : nullptr;
+#pragma unroll
+    for (int k = 0; k < NF; ++k) fbase[k] = k < a.n_own ? fc[a.own_flt[k].col] : nullptr;
+    // every load of a step is issued before the first value is looked at
+    auto load_tile = [&](int64_t t, SapQuad (&cq)[UQ][NC], SapQuad (&fq)[UQ][NF]) {
+#pragma unroll
+      for (int u = 0; u < UQ; ++u) {
+        const int64_t q = t * tile_q + (int64_t)u * kBlock + tid;
+        if (q < nq) {
+#pragma unroll
+          for (int k = 0; k < NC; ++k) {
+            if (k >= a.n_cols) break;
+            if (a.col_w8[k]) {
+              cq[u][k].lo = __builtin_nontemporal_load((const MQ_GLOBAL v4i32*)cbase[k] + q * 2);
+              cq[u][k].hi = __builtin_nontemporal_load((const MQ_GLOBAL v4i32*)cbase[k] + q * 2 + 1);
+            } else {
+              cq[u][k].lo = __builtin_nontemporal_load((const MQ_GLOBAL v4i32*)cbase[k] + q);
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < NF; ++k) {
+            if (k >= a.n_own) break;
+            if (a.own_type[k] == MI355Q_INT8) {
+              fq[u][k].lo.x = (int)__builtin_nontemporal_load((const MQ_GLOBAL uint32_t*)fbase[k] + q);
+            } else if (a.own_type[k] == MI355Q_INT32) {
+              fq[u][k].lo = __builtin_nontemporal_load((const MQ_GLOBAL v4i32*)fbase[k] + q);
+            } else {
+              fq[u][k].lo = __builtin_nontemporal_load((const MQ_GLOBAL v4i32*)fbase[k] + q * 2);
+              fq[u][k].hi = __builtin_nontemporal_load((const MQ_GLOBAL v4i32*)fbase[k] + q * 2 + 1);
+            }
+          }
+        } else if (q < nq_all) {  // (one lane per fragment)
+          const int left = (int)(n & 3);
+#pragma unroll
+          for (int k = 0; k < NC; ++k) {
+            if (k >= a.n_cols) break;
+            int64_t v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int64_t pos = (nq << 2) + (i < left ? i : left - 1);
+              v[i] = a.col_w8[k] ? load_one<int64_t>(cbase[k], pos) : (int64_t)load_one<int32_t>(cbase[k], pos);
+            }
+            sap_pack(v, a.col_w8[k] ? 8 : 4, cq[u][k]);
+          }
+#pragma unroll
+          for (int k = 0; k < NF; ++k) {
+            if (k >= a.n_own) break;
+            const int t8 = a.own_type[k];
+            int64_t v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const int64_t pos = (nq << 2) + (i < left ? i : left - 1);
+              v[i] = t8 == MI355Q_INT8    ? (int64_t)load_one<int8_t>(fbase[k], pos)
+                     : t8 == MI355Q_INT32 ? (int64_t)load_one<int32_t>(fbase[k], pos)
+                                          : load_one<int64_t>(fbase[k], pos);
+            }
+            sap_pack(v, t8 == MI355Q_INT8 ? 1 : t8 == MI355Q_INT32 ? 4 : 8, fq[u][k]);
+          }
+        }
+      }
+    };
+    auto tile_rows = [&](int64_t t, const SapQuad (&cq)[UQ][NC], const SapQuad (&fq)[UQ][NF]) {
+#pragma unroll
+      for (int u = 0; u < UQ; ++u) {
+        const int64_t q = t * tile_q + (int64_t)u * kBlock + tid;
+        const uint32_t valid = q < nq ? 15u : q < nq_all ? (1u << (int)(n & 3)) - 1u : 0u;
+        quad_rows(cq[u], fq[u], valid);
+      }
+    };
+    SapQuad cur_c[UQ][NC], cur_f[UQ][NF];
+#pragma unroll
+    for (int u = 0; u < UQ; ++u) {
+#pragma unroll
+      for (int k = 0; k < NC; ++k) cur_c[u][k].lo = cur_c[u][k].hi = v4i32{0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < NF; ++k) cur_f[u][k].lo = cur_f[u][k].hi = v4i32{0, 0, 0, 0};
+    }
+    // (the starting workgroup rotates per fragment so that short fragments still spread over the grid)
+    int64_t t = (blockIdx.x + (int64_t)f * 7) % gridDim.x;
+    if constexpr (PF) {
+      SapQuad nxt_c[UQ][NC], nxt_f[UQ][NF];
+#pragma unroll
+      for (int u = 0; u < UQ; ++u) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k) nxt_c[u][k] = cur_c[u][k];
+#pragma unroll
+        for (int k = 0; k < NF; ++k) nxt_f[u][k] = cur_f[u][k];
+      }
+      if (t < n_tiles) load_tile(t, nxt_c, nxt_f);
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+      for (; t < n_tiles; t += gridDim.x) {  // (uniform)
+#pragma unroll
+        for (int u = 0; u < UQ; ++u) {
+#pragma unroll
+          for (int k = 0; k < NC; ++k) cur_c[u][k] = nxt_c[u][k];
+#pragma unroll
+          for (int k = 0; k < NF; ++k) cur_f[u][k] = nxt_f[u][k];
+        }
+        if (t + gridDim.x < n_tiles) load_tile(t + gridDim.x, nxt_c, nxt_f);
+        tile_rows(t, cur_c, cur_f);
+      }
+    } else {
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+      for (; t < n_tiles; t += gridDim.x) {
+        load_tile(t, cur_c, cur_f);
+        tile_rows(t, cur_c, cur_f);
+      }
+    }
+  }
+  if (err) atomicCAS(a.d_err, 0, err);
+
+  // wave reduce, then one fold per workgroup in LDS (the epilogue of k_scan_agg)
+  __shared__ unsigned long long s_rows[kBlock / 64];
+  __shared__ SapAcc s_acc[kBlock / 64][kApMaxArgs];
+  rows_passing = wave_sum_u64(rows_passing);
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int c = 0; c < kApMaxArgs; ++c) {
+    if (c >= a.n_args) break;
+    SapAcc r;
+    r.cnt = wave_sum_u64(acc[c].cnt);
+    if (a.arg_type[c] == MI355Q_DOUBLE) {
+      r.sum = dbl_bits(sap_wave_sum_f64(bits_dbl(acc[c].sum)));
+      r.mn = sap_wave_best<true, false>(acc[c].mn);
+      r.mx = sap_wave_best<true, true>(acc[c].mx);
+    } else {
+      r.sum = (int64_t)wave_sum_i64((long long)acc[c].sum);
+      r.mn = sap_wave_best<false, false>(acc[c].mn);
+      r.mx = sap_wave_best<false, true>(acc[c].mx);
+    }
+    if (lane == 0) s_acc[wave][c] = r;
+  }
+  if (lane == 0) s_rows[wave] = rows_passing;
+  __syncthreads();
+  if (tid != 0) return;
+  unsigned long long rows = 0;
+  for (int w = 0; w < kBlock / 64; ++w) rows += s_rows[w];
+  if (!rows) return;  // nothing passed in this workgroup: the slots keep what they have
+  // the workgroup's partial row, as the row function would have left it in a private buffer
+  int64_t part[MI355Q_MAX_SLOTS];
+  for (int j = 0; j < a.slot_count; ++j) part[j] = a.init_vals[j];
+  for (int i = 0; i < a.n_targets; ++i) {
+    const DevTarget& tg = a.targets[i];
+    const int cs = a.target_arg[i];
+    if (cs < 0) {
+      part[tg.slot] = (int64_t)rows;
+      continue;
+    }
+    const bool fp = a.arg_type[cs] == MI355Q_DOUBLE;
+    SapAcc r = s_acc[0][cs];
+    for (int w = 1; w < kBlock / 64; ++w) {
+      const SapAcc& o = s_acc[w][cs];
+      r.cnt += o.cnt;
+      if (fp) {
+        r.sum = dbl_bits(bits_dbl(r.sum) + bits_dbl(o.sum));
+        r.mn = bits_dbl(o.mn) < bits_dbl(r.mn) ? o.mn : r.mn;
+        r.mx = bits_dbl(r.mx) < bits_dbl(o.mx) ? o.mx : r.mx;
+      } else {
+        r.sum = (int64_t)((uint64_t)r.sum + (uint64_t)o.sum);
+        r.mn = o.mn < r.mn ? o.mn : r.mn;
+        r.mx = r.mx < o.mx ? o.mx : r.mx;
+      }
+    }
+    switch (tg.agg) {
+      case MI355Q_COUNT: part[tg.slot] = (int64_t)r.cnt; break;
+      case MI355Q_AVG:
+        part[tg.slot + 1] = (int64_t)r.cnt;
+        [[fallthrough]];
+      case MI355Q_SUM:
+        if (r.cnt) part[tg.slot] = r.sum;
+        break;
+      case MI355Q_MIN:
+        if (r.cnt) part[tg.slot] = r.mn;
+        break;
+      default:
+        if (r.cnt) part[tg.slot] = r.mx;
+    }
+  }
+  for (int i = 0; i < a.n_targets; ++i) reduce_target<true>(a.targets[i], a.init_vals, a.out, part);
+}
+
+// the kernel's arguments from the lowered plan's quals and targets + the arguments' description; false: not this family
+bool sap_args(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, ScanAggProgArgs* out) {
+  ScanAggProgArgs& a = *out;
+  std::memset(&a, 0, sizeof(a));
+  if (p.desc_type != MI355Q_NON_GROUPED_AGGREGATE || p.join_col >= 0 || p.bf_active || p.slot_width != 8 || p.n_quals > MI355Q_MAX_QUALS ||
+      ap.n_args < 1 || ap.n_args > kApMaxArgs || ap.n_cols < 1 || ap.n_cols > kApMaxCols || p.n_targets > MI355Q_MAX_TARGETS)
+    return false;
+  a.n_cols = ap.n_cols;
+  a.n_args = ap.n_args;
+  a.n_progs = ap.n_progs;
+  a.n_frags = fv.n_frags;
+  a.n_cols_table = fv.n_cols;
+  a.n_targets = p.n_targets;
+  a.slot_count = p.slot_count;
+  for (int k = 0; k < ap.n_cols; ++k) {
+    if (!rp_type_ok(ap.col_type[k]) || ap.col[k] < 0 || ap.col[k] >= fv.n_cols || !all_aligned16(fv, ap.col[k])) return false;
+    a.col[k] = ap.col[k];
+    a.col_w8[k] = ap.col_type[k] == MI355Q_INT32 ? 0 : 1;
+  }
+  for (int c = 0; c < ap.n_args; ++c) {
+    a.arg_slot[c] = c < ap.n_progs ? 0 : ap.arg_slot[c];
+    a.arg_type[c] = ap.arg_type[c];
+    a.arg_nullable[c] = ap.arg_nullable[c];
+    a.prog[c] = ap.prog[c];
+  }
+  for (int i = 0; i < p.n_targets; ++i) {
+    a.targets[i] = p.targets[i];
+    a.target_arg[i] = ap.target_arg[i];
+    if (ap.target_arg[i] < 0) continue;
+    const int agg = p.targets[i].agg;
+    a.arg_need[ap.target_arg[i]] |= (agg == MI355Q_SUM || agg == MI355Q_AVG) ? 2 : agg == MI355Q_MIN ? 4 : agg == MI355Q_MAX ? 8 : 0;
+  }
+  for (int j = 0; j < MI355Q_MAX_SLOTS; ++j) a.init_vals[j] = p.init_vals[j];
+  // the range quals, merged per column as k_scan_agg merges them
+  RangeFilter flt[MI355Q_MAX_QUALS];
+  int32_t flt_type[MI355Q_MAX_QUALS];
+  for (int i = 0; i < p.n_quals; ++i) {
+    if (p.quals[i].col < 0 || p.quals[i].col >= fv.n_cols || !make_range_filter(p.quals[i], &flt[i], true)) return false;
+    flt_type[i] = p.quals[i].type;
+    if (!all_aligned16(fv, p.quals[i].col)) return false;
+  }
+  const int n_flt = merge_range_filters(flt, flt_type, p.n_quals);
+  if (n_flt > kSapFlt) return false;
+  for (int i = 0; i < n_flt; ++i) {
+    int slot = -1;
+    for (int k = 0; k < ap.n_cols; ++k)
+      if (ap.col[k] == flt[i].col && ap.col_type[k] == flt_type[i]) slot = k;
+    if (slot >= 0) {
+      a.sh_flt[a.n_shared] = flt[i];
+      a.sh_slot[a.n_shared++] = slot;
+    } else {
+      a.own_flt[a.n_own] = flt[i];
+      a.own_type[a.n_own++] = flt_type[i];
+    }
+  }
+  return true;
+}
+
 }  // namespace
+
+bool scan_agg_prog_eligible(const DevPlan& p, const AggProgArgs& ap, const FragView& fv) {
+  ScanAggProgArgs a;
+  return sap_args(p, ap, fv, &a);
+}
+
+hipError_t launch_scan_agg_prog(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int64_t* out, int32_t* d_err, int n_cus,
+                                hipStream_t s, LaunchStats* st) {
+  ScanAggProgArgs a;
+  if (!sap_args(p, ap, fv, &a)) return hipErrorInvalidValue;
+  a.cols = fv.d_cols;
+  a.num_rows = fv.d_num_rows;
+  a.out = out;
+  a.d_err = d_err;
+  st->kernel_name = "k_scan_agg_prog";
+  st->n_launches = 1;
+  st->variant = 0;
+  // two operand columns and at most one column read for the filter alone (SUM(a * b) WHERE c < k): two quads per column
+  // in flight and the next tile's behind them; else one quad of up to four + four columns (no room for the next tile's)
+  const bool lean = a.n_cols <= 2 && a.n_own <= 1;
+  const int bpc = tune_knobs().blocks_per_cu > 0 ? tune_knobs().blocks_per_cu : 2;
+  const int64_t want = (fv.max_frag_rows / 4 + kBlock * (lean ? 2 : 1)) / (kBlock * (lean ? 2 : 1));
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)n_cus * bpc, want));
+  rec(st->k_start, s);
+  if (lean) hipLaunchKernelGGL((k_scan_agg_prog<2, 1, 2, true>), dim3((unsigned)grid), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL((k_scan_agg_prog<kApMaxCols, kSapFlt, 1, false>), dim3((unsigned)grid), dim3(kBlock), 0, s, a);
+  rec(st->k_stop, s);
+  return hipGetLastError();
+}
 
 int64_t filter_mask_chunk_bytes(int64_t n_rows) { return ((((n_rows + 3) >> 2) << 2) + 15) & ~(int64_t)15; }
 

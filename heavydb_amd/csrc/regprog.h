@@ -16,7 +16,8 @@
 //     evaluation order of the checks) stated once, in expr.h.
 // Consumers: the atoms of a filter compiled at plan time (boolfilter.h: an atom is then the BOOLEAN such a program leaves;
 // evaluated by the row-mask pre-pass, kernels_filter.hip), the typed expression targets of the Projection family
-// (kernels_proj.hip k_proj_fast).
+// (kernels_proj.hip k_proj_fast), the arguments of non-grouped aggregates (AggProgArgs below; evaluated by the scan itself,
+// kernels_filter.hip k_scan_agg_prog).
 // Programs that do not fit (CASE, more than two live values, INT8 / INT16 / FLOAT arithmetic, encoded columns, values of
 // earlier expressions) keep the interpreter (expr.h eval_expr_rows).
 #pragma once
@@ -153,6 +154,92 @@ inline bool rp_compile(const DevExpr& e, int first, int last, int n_phys_cols, S
   p.type = types[0];
   p.nullable = nulls[0] ? 1 : 0;
   return true;
+}
+
+// ---- host: the ARGUMENTS of a step's aggregates as programs.  `d` is the plan over the LOWERED columns (expression k is
+// column xs.n_cols + k there), so a DevTarget states the type and the NULL rule its argument has on the two-pass path
+// (k_project, then the plain-column step); a consumer that takes this description evaluates the same thing in registers.
+// The arguments are the distinct columns the targets aggregate: the expressions first (argument k < n_progs is prog[k],
+// expression k of the plan), then plain unencoded INT32 / INT64 / DOUBLE columns.  Together they read at most kApMaxCols
+// physical columns, the consumer's operand slots.  Nothing in it is about WHERE the aggregates go: a grouped family can
+// take it as it is.
+constexpr int kApMaxArgs = 4, kApMaxCols = 4;
+struct AggProgArgs {
+  int32_t n_cols, n_args, n_progs, pad_;
+  int32_t col[kApMaxCols], col_type[kApMaxCols];            // operand slot -> physical column, its plain type
+  int32_t arg_slot[kApMaxArgs];                             // a plain-column argument's operand slot
+  int32_t arg_type[kApMaxArgs], arg_nullable[kApMaxArgs];   // DevTarget::arg_type / skip_null of the targets over it
+  int32_t arg_col[kApMaxArgs];                              // the argument's column in the lowered plan
+  int32_t target_arg[MI355Q_MAX_TARGETS];                   // -1 = COUNT(*)
+  RegProg prog[kApMaxArgs];
+};
+// false: the step is not one this form states (the caller keeps the interpreter pass): an aggregate kind other than
+// COUNT / SUM / MIN / MAX / AVG, an inner-table or FLOAT argument, an expression no target aggregates, one that does not
+// compile (rp_compile) or divides, a BOOLEAN result, a type or NULL rule the targets do not agree on, more arguments or
+// operand columns than there is room for.
+inline bool agg_prog_args_of(const DevPlan& d, const DevExprSet& xs, AggProgArgs* out) {
+  AggProgArgs& a = *out;
+  a = AggProgArgs{};
+  const int n_phys = xs.n_cols;
+  for (int i = 0; i < d.n_targets; ++i) {
+    const DevTarget& t = d.targets[i];
+    a.target_arg[i] = -1;
+    if (t.table != 0 || t.arg_f32) return false;
+    if (t.agg == MI355Q_COUNT && t.col < 0) continue;
+    if (t.agg != MI355Q_COUNT && t.agg != MI355Q_SUM && t.agg != MI355Q_MIN && t.agg != MI355Q_MAX && t.agg != MI355Q_AVG) return false;
+    if (t.col < 0 || t.col >= n_phys + xs.n || !rp_type_ok(t.arg_type)) return false;
+  }
+  auto slot_of = [&](int c) -> int {
+    for (int k = 0; k < a.n_cols; ++k)
+      if (a.col[k] == c) return k;
+    if (a.n_cols >= kApMaxCols) return -1;
+    a.col[a.n_cols] = c;
+    return a.n_cols++;
+  };
+  auto add_arg = [&](int col) -> bool {  // the targets over `col` become one argument
+    int type = 0, nullable = 0, n = 0;
+    for (int i = 0; i < d.n_targets; ++i) {
+      const DevTarget& t = d.targets[i];
+      if (t.col != col || (t.agg == MI355Q_COUNT && t.col < 0)) continue;
+      if (n && (type != t.arg_type || nullable != t.skip_null)) return false;  // one column, two NULL conventions
+      type = t.arg_type;
+      nullable = t.skip_null;
+      a.target_arg[i] = a.n_args;
+      ++n;
+    }
+    if (!n || a.n_args >= kApMaxArgs) return false;
+    a.arg_type[a.n_args] = type;
+    a.arg_nullable[a.n_args] = nullable;
+    a.arg_col[a.n_args] = col;
+    ++a.n_args;
+    return true;
+  };
+  for (int k = 0; k < xs.n; ++k) {
+    if (!add_arg(n_phys + k)) return false;  // (an expression that is nobody's argument included)
+    RegProg& p = a.prog[k];
+    if (!rp_compile(xs.e[k], 0, xs.e[k].n_nodes - 1, n_phys, slot_of, &p)) return false;
+    if (p.has_divmod || !rp_type_ok(p.type) || p.type != a.arg_type[k]) return false;
+    ++a.n_progs;
+  }
+  for (int i = 0; i < d.n_targets; ++i) {
+    const DevTarget& t = d.targets[i];
+    if (t.col < 0 || t.col >= n_phys || a.target_arg[i] >= 0) continue;
+    if (!add_arg(t.col)) return false;
+    const int slot = slot_of(t.col);
+    if (slot < 0) return false;
+    a.arg_slot[a.n_args - 1] = slot;
+    a.col_type[slot] = t.arg_type;
+  }
+  // an operand column's type: what the COL nodes that read it say (rp_compile: the column's plain type code)
+  for (int k = 0; k < xs.n; ++k)
+    for (int i = 0; i < xs.e[k].n_nodes; ++i) {
+      const DevExprNode& n = xs.e[k].nodes[i];
+      if (n.op != MI355Q_EX_COL) continue;
+      const int slot = slot_of(n.arg);
+      if (slot < 0 || (a.col_type[slot] && a.col_type[slot] != n.type)) return false;
+      a.col_type[slot] = n.type;
+    }
+  return a.n_args >= 1;
 }
 
 // ---- the typed members.  OP / T are compile-time constants: the compiler folds every decision ex_* takes on them.

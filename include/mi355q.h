@@ -571,6 +571,10 @@ typedef struct mi355q_exec_options {
 #define MI355Q_OPT_NO_LATTICE_PART 2048u  /* partitioned GROUP BY: the plain member (hashed records, keyed LDS tables) even where
                                             the key column is a lattice min + stride x i that the lattice member would
                                             aggregate by index (tests and bench.py --opt-flags compare the two) */
+#define MI355Q_OPT_NO_AGG_PROGRAMS 4096u  /* non-grouped aggregates of expressions: the interpreter pass (k_project) and a
+                                            plain-column step even where the arguments compile into two-register programs
+                                            that k_scan_agg_prog evaluates in registers (tests and tools/agg_prog_bench.py
+                                            compare the two) */
 
 /* per-call timing/selection report (what launchGpuCode logs,
  * QueryExecutionContext.cpp:334,364,579) */

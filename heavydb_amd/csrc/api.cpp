@@ -867,6 +867,7 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
     if (!async && (e = try_route(out, [&] { return execute_shifted_args(plan, in, o, out, report, reserved); })) != kNotTaken) return e;
     if (!async && (e = try_route(out, [&] { return execute_cast_key(plan, in, o, out, report, reserved); })) != kNotTaken) return e;
     if (!async && (e = try_route(out, [&] { return execute_agg_programs(plan, in, o, out, report, reserved); })) != kNotTaken) return e;
+    if (!async && (e = try_route(out, [&] { return execute_grouped_agg_programs(plan, in, o, out, report, reserved); })) != kNotTaken) return e;
     if (reserved) {  // the step proper runs on the lowered plan: reserve for that
       route_note("k_project");
       mi355q_plan lp;

@@ -315,6 +315,9 @@ int32_t execute_cast_key(const mi355q_plan* plan, const mi355q_inputs* in, const
 // (non-grouped aggregates whose arguments compile into two-register programs: one kernel, no projection pass)
 int32_t execute_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
                              mi355q_exec_report* report, int64_t* reserved);
+// (... and the few-groups GROUP BY steps of such arguments: k_groupby_lds_prog)
+int32_t execute_grouped_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                                     mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_projected(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
                           mi355q_result** out, mi355q_exec_report* report);
 // (the layout twins: columnar output through its row-wise form, 4-byte slots through the 8-byte layout)

@@ -1366,6 +1366,134 @@ int32_t execute_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, c
   return MI355Q_OK;
 }
 
+// The GROUPED half of the route above — SELECT g, SUM(a * b), COUNT(*) FROM t WHERE c < k GROUP BY g — for the few-groups
+// shapes: a perfect-hash layout over 1 - 3 plain INT32 / INT64 key columns whose table fits up to 8 windows of LDS.  The
+// reference compiles such arguments into the row function all the same (ArithmeticIR.cpp:39-431); here k_groupby_lds_prog
+// (kernels_lds.hip) keeps k_groupby_lds's replicated table and evaluates the arguments' programs on the values it has loaded:
+// one kernel, no temporary column (8 bytes per row and expression on the two-pass route, which falls back to several passes
+// once they exceed a third of the free memory), no synchronisation in between.  Type and NULL rule of an argument come from
+// the lowered plan's targets, as above.
+// Size rule: from 2^20 rows on, or when kernel_variant 2 asks for the large-input members (how the tests reach this route
+// with small tables).  The threshold is a routing constant — the one the compiled filter uses — not a measured crossover:
+// below it the two-pass step costs launches, not bandwidth.
+// Class rule (grouped_prog_class_on_by_default below): above the threshold a step takes the route BY DEFAULT only if its
+// class of arguments beat the two-pass route when measured.  None did, so today the route runs with kernel_variant 2 alone.
+// kNotTaken: baseline layouts, expression keys, division / CASE / BOOLEAN results, narrow, FLOAT or encoded operands, _IF
+// targets, joins, columnar or 4-byte-slot layouts, a compiled filter, more than 3 arguments, range quals on more than 4
+// distinct columns (or on more than 2 that are neither operand nor key columns), tables beyond 8 windows (regprog.h
+// agg_prog_args_of, lds_args.h make_lds_prog_args); that plan keeps the projection pass.
+//
+// A shape class is the type of the program arguments.  1 B rows, one INT32 key with 100 / 1000 groups, 50 % qual, this route
+// against the two passes (k_project, then k_perfect_lds), best of 7 steps, three alternating runs each
+// (profiles/agg_prog_grouped_bench_1b.jsonl):
+//   INT32   SUM(a * b)                                  11.42 - 11.45 ms  against   7.84 -  7.93   LOST
+//   INT64   SUM(CAST(a AS BIGINT) * CAST(b AS BIGINT))  13.47 - 13.52     against   9.98 - 10.13   LOST
+//   DOUBLE  SUM / MIN / AVG(p * 2.5 - q)                12.48 - 12.53     against  10.93 - 11.21   LOST
+// A class that loses stays on k_project by default; what the route removes there — the temporary columns, 8 bytes per row and
+// expression — is had by asking for it (kernel_variant 2).
+static bool grouped_prog_class_on_by_default(const AggProgArgs& ap) {
+  for (int k = 0; k < ap.n_progs; ++k) {
+    switch (ap.prog[k].type) {
+      case MI355Q_INT32: return false;   // lost by 3.5 ms per 1 B rows
+      case MI355Q_INT64: return false;   // lost by 3.4 ms
+      case MI355Q_DOUBLE: return false;  // lost by 1.3 ms
+      default: return false;
+    }
+  }
+  return false;  // (no program at all: not this route's step)
+}
+
+int32_t execute_grouped_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
+                                     mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  if (plan->n_exprs <= 0 || plan->n_group_cols < 1 || plan->n_group_cols > 3 || plan->join_outer_col >= 0 || plan->output_columnar_hint != 0 ||
+      o.force_generic || in->n_frags <= 0 || (o.flags & MI355Q_OPT_NO_GROUPED_AGG_PROGRAMS) || plan->n_quals < 0 ||
+      plan->n_quals > MI355Q_MAX_QUALS || plan->n_targets < 1 || plan->n_targets > MI355Q_MAX_TARGETS || step_bool_filter())
+    return kNotTaken;
+  for (int i = 0; i < plan->n_quals; ++i)
+    if (MI355Q_QUAL_OR_GROUP(plan->quals[i].op) != 0) return kNotTaken;
+  // an expression a qual or another expression reads is evaluated for every row: the projection pass's business
+  if (expr_qual_mask(*plan) != 0 || exprs_read_exprs(*plan)) return kNotTaken;
+  const int nf = in->n_frags, nc = plan->n_cols;
+  int64_t total_rows = 0, max_frag_rows = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
+    total_rows += in->num_rows[f];
+    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
+  }
+  if (o.kernel_variant != 2 && total_rows < ((int64_t)1 << 20)) return kNotTaken;  // (the size rule above)
+  mi355q_plan lp;
+  DevExprSet xs;
+  mi355q_qmd q;
+  DevPlan d;
+  if (lower_exprs(*plan, &lp, &xs, true) != MI355Q_OK || qmd_init(*plan, &q) != MI355Q_OK) return kNotTaken;
+  if (q.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || q.slot_width != 8 || q.output_columnar) return kNotTaken;
+  if (build_dev_plan(lp, q, &d) != MI355Q_OK) return kNotTaken;
+  AggProgArgs ap;
+  if (!agg_prog_args_of(d, xs, &ap)) return kNotTaken;
+  if (o.kernel_variant != 2 && !grouped_prog_class_on_by_default(ap)) return kNotTaken;  // (the class rule above)
+  // (the kernel reads physical columns only: the table it is handed is the stated one, nc columns per fragment)
+  FragView fv{nullptr, nullptr, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
+  const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
+  if (!lds_groupby_prog_eligible(d, ap, fv, n_cus)) return kNotTaken;
+  if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched, and there are no temporary columns
+    route_note("grouped aggregate arguments as register programs");
+    route_note("k_groupby_lds_prog");
+    *reserved = 0;
+    if (t_plan_only) return MI355Q_OK;
+  }
+  RouteScope rs(in->device_id, o.stream);
+  if (rs.status) return rs.status;
+  DeviceCtx& ctx = rs.ctx;
+  // column table | row counts | error words, one upload out of pinned memory (reserve: laid out only)
+  FragTable ft;
+  if (int32_t e = upload_frag_table(ctx, *in, nc, o.stream, reserved ? FragUpload::kNone : FragUpload::kAlways, &ft)) return e;
+  LaunchStats st;
+  if (report || reserved) {
+    while ((int)ctx.events.size() < 4) {
+      hipEvent_t ev;
+      HIP_TRY(hipEventCreate(&ev));
+      ctx.events.push_back(ev);
+    }
+    st.k_start = ctx.events[2];
+    st.k_stop = ctx.events[3];
+  }
+  if (reserved) return MI355Q_OK;
+  hipStream_t s = ft.s;
+  struct UploadGuard {  // the upload reads the SHARED pinned block: no return leaves it in flight
+    hipStream_t s;
+    bool armed;
+    ~UploadGuard() {
+      if (armed) (void)hipStreamSynchronize(s);
+    }
+  } upload_guard{s, true};
+  mi355q_result* res = nullptr;
+  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
+  ResultPtr owned(res);
+  fv.d_cols = ft.d_cols;
+  fv.d_num_rows = ft.d_rows;
+  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
+  HIP_TRY(launch_lds_groupby_prog(d, ap, fv, res->buf, ft.d_err, n_cus, s, &st));
+  // an error a passing row raised (7), or a key outside its declared range, ends the step with no result
+  int32_t* h_ret = (int32_t*)(ctx.h_meta + ctx.meta_bytes);
+  HIP_TRY(hipMemcpyAsync(h_ret, ft.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  upload_guard.armed = false;
+  const int32_t code = h_ret[0];
+  if (report) {  // a one-kernel step: its event pair is the step's time as well
+    std::memset(report, 0, sizeof(*report));
+    std::snprintf(report->kernel_name, sizeof(report->kernel_name), "%s", st.kernel_name);
+    if (hipEventElapsedTime(&report->kernel_ms, st.k_start, st.k_stop) != hipSuccess) report->kernel_ms = 0.f;
+    report->total_ms = report->kernel_ms;
+    report->n_launches = st.n_launches;
+    report->variant = st.variant;
+    report->rows_scanned = total_rows;
+    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
+  }
+  if (code) return code;
+  *out = owned.release();
+  return MI355Q_OK;
+}
+
 // Plans with projected expressions (mi355q_expr): scan / filter / PROJECT.  The expressions of a pass of
 // fragments are evaluated into dense temporary columns (k_project), the step runs on the lowered plan — where
 // those columns are ordinary inputs, so every kernel family applies — and the passes' results are folded with

@@ -389,6 +389,15 @@ bool scan_agg_prog_eligible(const DevPlan& p, const AggProgArgs& ap, const FragV
 hipError_t launch_scan_agg_prog(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int64_t* out, int32_t* d_err, int n_cus,
                                 hipStream_t s, LaunchStats* st);
 
+// ... and the GROUPED steps of the same arguments on a perfect-hash layout whose table fits up to 8 windows of LDS (1 - 3 plain
+// INT32 / INT64 key columns, up to 3 arguments over up to 4 operand columns, range quals on operand / key columns and on up
+// to 2 columns read for the filter alone): kernels_lds.hip k_groupby_lds_prog (lds_args.h make_lds_prog_args).  `p`: the plan
+// over the lowered columns.  d_err[0]: error 7 of a passing row, or MI355Q_ERR_OUT_OF_SLOTS for a key outside its declared
+// range.  variant 6: one window, 7: several.
+bool lds_groupby_prog_eligible(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int n_cus);
+hipError_t launch_lds_groupby_prog(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int64_t* out, int32_t* d_err,
+                                   int n_cus, hipStream_t s, LaunchStats* st);
+
 bool join_sum_eligible(const DevPlan& p, const FragView& fv);
 hipError_t launch_join_sum(const DevPlan& p, const FragView& fv, int64_t* out, int n_cus,
                            hipStream_t s, LaunchStats* st);

@@ -921,3 +921,66 @@ hipError_t launch_filter_mask(const BoolFilter& bf, const BoolFilter* d_bf, cons
 }
 
 }  // namespace mq
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The host simulation WITHOUT the LDS families (tests/hostsim: kernels_lds.hip is not part of that build, its members are
+// row-function stand-ins there) still links and takes the route of k_groupby_lds_prog: the member's own description decides
+// who is eligible (lds_args.h make_lds_prog_args), and a launch writes the arguments' values into temporary columns — what
+// k_project would have left, through this file's evaluator — and runs the lowered plan's row function over them.  An error
+// counts only for a row that passes the quals.  The simulation that compiles kernels_lds.hip for the host, and every
+// device build, have the kernel itself.
+#if defined(HOSTSIM_DEVICE_CODE) && !defined(HOSTSIM_REAL_FAST)
+#include <vector>
+
+#include "lds_args.h"
+
+namespace mq {
+
+bool lds_groupby_prog_eligible(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int n_cus) {
+  LdsProgArgs a;
+  return make_lds_prog_args(p, ap, fv, n_cus, tune_knobs().flags, &a);
+}
+hipError_t launch_lds_groupby_prog(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int64_t* out, int32_t* d_err, int n_cus,
+                                   hipStream_t, LaunchStats* st) {
+  LdsProgArgs a;
+  if (!make_lds_prog_args(p, ap, fv, n_cus, tune_knobs().flags, &a)) return hipErrorInvalidValue;
+  st->kernel_name = "k_groupby_lds_prog";
+  st->n_launches = 1;
+  st->variant = a.l.windows > 1 ? 7 : 6;
+  auto value = [](const int8_t* base, int type, int64_t pos) -> int64_t {
+    return type == MI355Q_INT32 ? (int64_t)((const int32_t*)base)[pos] : type == MI355Q_INT8 ? (int64_t)base[pos] : ((const int64_t*)base)[pos];
+  };
+  for (int f = 0; f < fv.n_frags; ++f) {
+    const int8_t* const* fc = fv.d_cols + (size_t)f * fv.n_cols;
+    const int64_t n = fv.d_num_rows[f];
+    std::vector<std::vector<int64_t>> tmp((size_t)a.n_progs, std::vector<int64_t>((size_t)n + 1));
+    std::vector<const int8_t*> cols(fc, fc + fv.n_cols);
+    for (int k = 0; k < a.n_progs; ++k) cols.push_back((const int8_t*)tmp[(size_t)k].data());
+    for (int64_t pos = 0; pos < n; ++pos) {
+      bool pass = true;
+      for (int i = 0; i < a.l.n_flt; ++i)
+        pass = pass && fast::filter_pass<int64_t>(a.l.flt[i], value(fc[a.l.flt[i].col], a.l.flt_type[i], pos));
+      int64_t vals[1][kApMaxCols] = {};
+      for (int c = 0; c < a.n_cols; ++c) vals[0][c] = value(fc[a.col[c]], a.col_w8[c] ? MI355Q_INT64 : MI355Q_INT32, pos);
+      for (int k = 0; k < a.n_progs; ++k) {
+        int64_t v[1];
+        int32_t e[1];
+        rp_eval<1, kApMaxCols, false>(a.prog[k], vals, v, e);
+        if (e[0] && pass) {
+          atomicCAS(d_err, 0, e[0]);
+          return hipSuccess;
+        }
+        if (a.l.v[k].type == MI355Q_INT32) ((int32_t*)tmp[(size_t)k].data())[pos] = (int32_t)v[0];  // (a plain column of the argument's type)
+        else tmp[(size_t)k][(size_t)pos] = v[0];
+      }
+      if (const int32_t e = process_row<true>(p, cols.data(), pos, out, nullptr)) {
+        atomicCAS(d_err, 0, e);
+        return hipSuccess;
+      }
+    }
+  }
+  return hipSuccess;
+}
+
+}  // namespace mq
+#endif

@@ -41,7 +41,6 @@ using namespace fast;
 namespace {
 
 constexpr int kLdsBlock = 1024;
-constexpr size_t kLdsBudget = 152 * 1024;
 
 struct RawQ {
   v4i32 lo, hi;
@@ -1043,39 +1042,395 @@ __global__ __launch_bounds__(kLdsBlock) void k_groupby_lds_typed(const int8_t* c
   }
 }
 
+// The epilogue of k_groupby_lds_prog below: k_groupby_lds's fold of the replicas into replica 0 and its merge of replica 0
+// into the output table, as functions with the workgroup's size a parameter.  A COPY: k_groupby_lds keeps its own text —
+// calling these from it changed the register count of one of its instantiations (<1, 1, 3, 1>: 93 -> 92 VGPRs), and the
+// existing members' code objects were to stay as they are.
+// lds_fold_replicas: false = the attempt is lost (a baseline table: the replicas together hold more groups than one does).
+template <int NV, int BLOCK>
+MQ_D bool lds_fold_replicas(char* smem, const LdsArgs& a, int t, volatile uint32_t* s_full, int32_t* d_err) {
+  // ---- fold replicas 1 .. K-1 into replica 0
+  const uint32_t K = 1u << a.copies_lg;
+  const uint32_t ne = a.entries;
+  char* const rep0 = smem;
+  for (uint32_t r = 1; r < K; ++r) {
+    char* rep = smem + (size_t)r * a.copy_bytes;
+    for (uint32_t e = t; e < ne; e += BLOCK) {
+      const uint32_t rows = ((uint32_t*)(rep + a.off_rows))[e];
+      if (!rows) continue;
+      uint32_t e0 = e;
+      if (a.baseline) {
+        const int64_t fk = ((int64_t*)(rep + a.off_keys))[e];
+        e0 = lds_key_slot((int64_t*)(rep0 + a.off_keys), ne, fk, lds_key_mix(fk));
+        if (e0 == kNoSlot) {  // the replicas together hold more groups than one does
+          if (atomicExch((uint32_t*)s_full, 1u) == 0u) atomicExch(d_err + 1, 1);
+          continue;
+        }
+      }
+      atomicAdd((uint32_t*)(rep0 + a.off_rows) + e0, rows);
+#pragma unroll
+      for (int c = 0; c < NV; ++c) {
+        if (c >= a.n_vals) break;
+        const LdsVal& v = a.v[c];
+        const bool fp = v.type == MI355Q_DOUBLE;
+        if (v.off_cnt >= 0) atomicAdd((uint32_t*)(rep0 + v.off_cnt) + e0, ((uint32_t*)(rep + v.off_cnt))[e]);
+        if (v.off_sum >= 0) {
+          if (fp) atomicAdd((double*)(rep0 + v.off_sum) + e0, ((double*)(rep + v.off_sum))[e]);
+          else atomicAdd((unsigned long long*)(rep0 + v.off_sum) + e0, ((unsigned long long*)(rep + v.off_sum))[e]);
+        }
+        if (v.off_min >= 0) {
+          if (fp) lds_min_f64((int64_t*)(rep0 + v.off_min) + e0, ((double*)(rep + v.off_min))[e]);
+          else atomicMin((long long*)(rep0 + v.off_min) + e0, ((long long*)(rep + v.off_min))[e]);
+        }
+        if (v.off_max >= 0) {
+          if (fp) lds_max_f64((int64_t*)(rep0 + v.off_max) + e0, ((double*)(rep + v.off_max))[e]);
+          else atomicMax((long long*)(rep0 + v.off_max) + e0, ((long long*)(rep + v.off_max))[e]);
+        }
+      }
+    }
+    __syncthreads();  // (baseline: inserts into replica 0 of one round must be visible to the next)
+    if (*s_full) return false;
+  }
+  return true;
+}
+// e_lo: the first entry index of the workgroup's window (perfect hash)
+template <int NK, int NV, int BLOCK>
+MQ_D void lds_flush_replica0(char* rep0, const LdsArgs& a, const DevPlan& p, uint32_t e_lo, int t, int64_t* out, int32_t* d_err) {
+  const uint32_t ne = a.entries;
+  // ---- merge every live entry of replica 0 into the output table with the reduce rule
+  for (uint32_t e = t; e < ne; e += BLOCK) {
+    const uint32_t rows = ((const uint32_t*)(rep0 + a.off_rows))[e];
+    if (!rows) continue;
+    int64_t key0 = 0, key1 = 0, key2 = 0;  // the group columns' values as decoded (what a projection shows)
+    int64_t* slots;
+    if (a.baseline) {
+      key0 = ((const int64_t*)(rep0 + a.off_keys))[e];
+      slots = baseline_find_or_insert(out, (uint32_t)p.entry_count, p.row_quad, p.key_width, key0);
+      if (!slots) {
+        atomicCAS(d_err, 0, -1);  // out of group slots: the caller grows the table and retries
+        continue;
+      }
+    } else {
+      int64_t tk0 = 0, tk1 = 0, tk2 = 0;
+      if ((uint64_t)e_lo + e >= (uint64_t)p.entry_count) continue;  // (padding of the last window)
+      uint32_t rem = e_lo + e;
+#pragma unroll
+      for (int g = NK - 1; g >= 0; --g) {  // entry index -> key components (mul_g ascending with g)
+        if (g >= a.n_keys) continue;
+        const int64_t d = (int64_t)(rem / (uint32_t)a.key_mul[g]);
+        rem -= (uint32_t)(d * a.key_mul[g]);
+        const int64_t tk = d + a.key_min[g];
+        const int64_t orig = (a.key_translate[g] && tk == a.key_null_key[g])
+                                 ? (a.key_type[g] == MI355Q_INT32 ? (int64_t)INT32_MIN : INT64_MIN) : tk;
+        if (g == 0) { tk0 = tk; key0 = orig; } else if (g == 1) { tk1 = tk; key1 = orig; } else { tk2 = tk; key2 = orig; }
+      }
+      int64_t* row = out + (size_t)(e_lo + e) * p.row_quad;
+      if (!p.keyless) {
+        if (MQ_LOAD64(row) == kEmptyKey64) {
+          if (a.n_keys > 2) MQ_STORE64(row + 2, tk2);
+          if (a.n_keys > 1) MQ_STORE64(row + 1, tk1);
+          MQ_STORE64(row, tk0);
+        }
+        slots = row + a.n_keys;
+      } else {
+        slots = row;
+      }
+    }
+    // the entry's partial row, slot by slot (static slot indices: no private-memory array), merged with the reduce rule
+#pragma unroll
+    for (int i = 0; i < MI355Q_MAX_TARGETS; ++i) {
+      if (i >= p.n_targets) break;
+      const DevTarget& tg = p.targets[i];
+      if (tg.slot < 0) continue;
+      int64_t v0 = p.init_vals[tg.slot], v1 = tg.agg == MI355Q_AVG ? p.init_vals[tg.slot + 1] : 0;
+      if (tg.agg == MI355Q_PROJECT_KEY) {
+        v0 = tg.key_idx == 0 ? key0 : tg.key_idx == 1 ? key1 : key2;
+      } else {
+        const int c = a.target_v[i];
+        if (c < 0) {
+          v0 = (int64_t)rows;
+        } else {
+          const LdsVal v = c == 0 ? a.v[0] : (NV > 1 && c == 1) ? a.v[NV > 1 ? 1 : 0] : a.v[NV > 2 ? 2 : 0];
+          // rows with a value: the non-NULL counter where one is kept (nullable column), else every row
+          const uint32_t cnt = v.off_cnt >= 0 ? ((const uint32_t*)(rep0 + v.off_cnt))[e] : rows;
+          switch (tg.agg) {
+            case MI355Q_COUNT: v0 = (int64_t)cnt; break;
+            case MI355Q_AVG:
+              v1 = (int64_t)cnt;
+              [[fallthrough]];
+            case MI355Q_SUM:
+              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_sum))[e];
+              break;
+            case MI355Q_MIN:
+              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_min))[e];
+              break;
+            default:
+              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_max))[e];
+          }
+        }
+      }
+      // reduce_target reads that_slots[t.slot (+ 1)]: hand it a two-quad window positioned at the target's slot
+      int64_t win[2] = {v0, v1};
+      DevTarget lt = tg;
+      lt.slot = 0;
+      reduce_target<true>(lt, p.init_vals + tg.slot, slots + tg.slot, win);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// k_groupby_lds_prog: GROUPED aggregates whose ARGUMENTS are expressions — SELECT g, SUM(a * b), COUNT(*) WHERE c < k
+// GROUP BY g — in one pass: k_groupby_lds's table (K replicas in dynamic LDS, lane l on replica l % K, lds_update, windows,
+// the fold and the flush above) around k_scan_agg_prog's evaluator (kernels_filter.hip: the operand columns as 16-byte
+// non-temporal quads, the range quals on the values as loaded — a 4-bit pass mask —, the arguments as two-register programs
+// in static LDS run on the four rows of a quad together, ONE copy of the evaluator in the kernel).  The two-pass route
+// (k_project writes 8 bytes per row and expression, a grouped family reads them back) moves 16 B/row/expression more, holds
+// the temporary columns and synchronises in between.
+//   geometry  512-lane workgroups, one per CU (kLdsBudget of dynamic LDS): two waves per SIMD and 256 VGPRs per lane, which
+//             the four-rows-wide 64-bit evaluator needs (k_groupby_lds's 1024 lanes leave 128).  One quad per column in
+//             flight, no prefetch of the next tile.
+//   rows      a fragment's last partial quad goes down the same path, its rows loaded one by one by the lane it falls to (a
+//             row past the end repeats the last one and is never valid).
+//   errors    the row function evaluates a target's expression only for a row that passed the quals: an error (7) counts
+//             only where the quad's pass bit is set, and goes to d_err[0] with one atomicCAS.
+// NC / NF / NK / NV: operand columns, filter-only columns, key columns loaded on their own, arguments this member holds
+// registers for.  perfect-hash layouts only (make_lds_prog_args).
+static_assert(sizeof(LdsProgArgs) + sizeof(DevPlan) <= 3968, "k_groupby_lds_prog takes its arguments by value: the kernel argument segment holds 4 KB");
+template <int NC, int NF, int NK, int NV>
+__global__ __launch_bounds__(kLdsProgBlock) void k_groupby_lds_prog(const int8_t* const* __restrict__ cols,
+                                                                     const int64_t* __restrict__ num_rows, int n_frags, int n_cols,
+                                                                     LdsProgArgs a, DevPlan p, int64_t* __restrict__ out,
+                                                                     int32_t* __restrict__ d_err) {
+  constexpr int NFA = NF > 0 ? NF : 1;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ RegProg s_prog[kLdsVals];
+  const LdsArgs& l = a.l;
+  const int t = threadIdx.x;
+  {
+    const int32_t* src = (const int32_t*)a.prog;
+    int32_t* dst = (int32_t*)s_prog;
+    for (int i = t; i < (int)(sizeof(RegProg) / 4) * a.n_progs; i += kLdsProgBlock) dst[i] = src[i];
+  }
+  const uint32_t K = 1u << l.copies_lg;
+  const uint32_t ne = l.entries;
+  const uint32_t T = l.windows;
+  const WinMap wm = lds_window_map(T, l.xcd_aware);
+  const uint32_t stripe = wm.stripe, n_stripes = wm.n_stripes;
+  const uint32_t e_lo = wm.win * ne;  // first entry index of the window
+  // ---- initialise every replica: counters 0, sums 0, min / max identities (as k_groupby_lds)
+  for (uint32_t r = 0; r < K; ++r) {
+    char* rep = smem + (size_t)r * l.copy_bytes;
+    for (uint32_t e = t; e < ne; e += kLdsProgBlock) {
+      ((uint32_t*)(rep + l.off_rows))[e] = 0;
+#pragma unroll
+      for (int c = 0; c < NV; ++c) {
+        if (c >= l.n_vals) break;
+        const LdsVal& v = l.v[c];
+        const bool fp = v.type == MI355Q_DOUBLE;
+        if (v.off_cnt >= 0) ((uint32_t*)(rep + v.off_cnt))[e] = 0;
+        if (v.off_sum >= 0) ((int64_t*)(rep + v.off_sum))[e] = 0;
+        if (v.off_min >= 0) ((int64_t*)(rep + v.off_min))[e] = fp ? 0x7ff0000000000000ll : INT64_MAX;
+        if (v.off_max >= 0) ((int64_t*)(rep + v.off_max))[e] = fp ? (int64_t)0xfff0000000000000ull : INT64_MIN;
+      }
+    }
+  }
+  volatile uint32_t* const s_full = (volatile uint32_t*)(smem + ((size_t)l.copy_bytes << l.copies_lg));  // (never set: no baseline member)
+  if (t == 0) *s_full = 0u;
+  __syncthreads();
+  char* const my_rep = smem + (size_t)((uint32_t)t & (K - 1)) * l.copy_bytes;
+  bool bad = false;
+  int32_t err = 0;
+
+  // one quad of every column: the range quals on the values as loaded (a 4-bit pass mask), the programs on its four rows,
+  // then row by row the entry index, the window test and the updates
+  auto quad_rows = [&](const RawQ (&cq)[NC], const RawQ (&fq)[NFA], const RawQ (&kq)[NK], uint32_t valid) {
+    int64_t vals[4][NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) vals[i][k] = k >= a.n_cols ? 0 : a.col_w8[k] ? rawq_i64(cq[k], i) : (int64_t)rawq_i32(cq[k], i);
+    }
+    // key g of row i: an operand as loaded (wave-uniform selects), or the key's own quad
+    auto key_of = [&](int g, int i) -> int64_t {
+      const int slot = a.key_slot[g];
+      int64_t k = l.key_type[g] == MI355Q_INT32 ? (int64_t)rawq_i32(kq[g], i) : rawq_i64(kq[g], i);
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (slot == c) k = vals[i][c];
+      return k;
+    };
+    uint32_t pass = valid;
+#pragma unroll
+    for (int k = 0; k < kLdsProgFlt; ++k) {
+      if (k >= l.n_flt) break;
+      const int src = a.flt_src[k];
+      uint32_t m = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int64_t x = vals[i][0];
+#pragma unroll
+        for (int c = 1; c < NC; ++c)
+          if (src == LPS_OPERAND + c) x = vals[i][c];
+#pragma unroll
+        for (int g = 0; g < NK; ++g)
+          if (src == LPS_KEY + g) x = l.key_type[g] == MI355Q_INT32 ? (int64_t)rawq_i32(kq[g], i) : rawq_i64(kq[g], i);
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+          if (src == LPS_OWN + f) x = rawq_int(fq[f], a.own_type[f], i);
+        m |= (filter_pass<int64_t>(l.flt[k], x) ? 1u : 0u) << i;
+      }
+      pass &= m;
+    }
+    // every passing row's entry index (the perfect-hash arithmetic of k_groupby_lds, NULL keys translated) and the window
+    // test, BEFORE the programs run: the keys' registers are free while the evaluator needs its own.  kNoSlot: no update
+    uint32_t ent[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int64_t idx = 0;
+      bool in_range = true;
+#pragma unroll
+      for (int g = 0; g < NK; ++g) {
+        if (g >= l.n_keys) break;
+        int64_t k = key_of(g, i);
+        if (l.key_translate[g] && k == (l.key_type[g] == MI355Q_INT32 ? (int64_t)INT32_MIN : INT64_MIN)) k = l.key_null_key[g];
+        const int64_t d = k - l.key_min[g];
+        in_range = in_range && d >= 0 && d < l.key_card[g];
+        idx += d * l.key_mul[g];
+      }
+      in_range = in_range && (uint64_t)idx < (uint64_t)p.entry_count;
+      const bool passes = ((pass >> i) & 1u) != 0;
+      bad = bad || (passes && !in_range);
+      const uint32_t e = (uint32_t)idx - e_lo;
+      ent[i] = (passes && in_range && e < ne) ? e : kNoSlot;  // (e >= ne: another window's row)
+    }
+    int64_t av[NV][4];
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      // a plain-column argument: the operand as loaded (wave-uniform selects, never a run-time index into registers)
+      const int slot = c >= a.n_progs && c < a.n_args ? a.arg_slot[c] : 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int64_t x = vals[i][0];
+#pragma unroll
+        for (int k = 1; k < NC; ++k)
+          if (slot == k) x = vals[i][k];
+        av[c][i] = x;
+      }
+    }
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int k = 0; k < a.n_progs; ++k) {
+      int64_t outv[4];
+      int32_t e4[4];
+      rp_eval<4, NC, false>(s_prog[k], vals, outv, e4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (e4[i] && ((pass >> i) & 1u) && !err) err = e4[i];
+#pragma unroll
+      for (int c = 0; c < NV; ++c) {
+        if (k != c) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) av[c][i] = outv[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t e = ent[i];
+      if (e == kNoSlot) continue;
+      atomicAdd((uint32_t*)(my_rep + l.off_rows) + e, 1u);
+#pragma unroll
+      for (int c = 0; c < NV; ++c) {
+        if (c >= l.n_vals) break;
+        lds_update(my_rep, l.v[c], e, av[c][i]);
+      }
+    }
+  };
+
+  for (int f = 0; f < n_frags; ++f) {
+    const int8_t* const* fc = cols + (size_t)f * n_cols;
+    const int64_t n = num_rows[f];
+    const int64_t nq = n >> 2;
+    // the fragment's quads, its last partial one included: the tile loop below is the only path through the fragment
+    const int64_t nq_all = (n + 3) >> 2;
+    const int64_t n_tiles = (nq_all + kLdsProgBlock - 1) / kLdsProgBlock;
+    const int8_t *cbase[NC], *fbase[NFA], *kbase[NK];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) cbase[k] = k < a.n_cols ? fc[a.col[k]] : nullptr;
+#pragma unroll
+    for (int k = 0; k < NFA; ++k) fbase[k] = k < a.n_own ? fc[a.own_col[k]] : nullptr;
+#pragma unroll
+    for (int g = 0; g < NK; ++g) kbase[g] = (g < l.n_keys && a.key_slot[g] < 0) ? fc[l.key_col[g]] : nullptr;
+    // (the starting stripe rotates per fragment so that short fragments still spread over the grid)
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int64_t tl = (stripe + (int64_t)f * 7) % n_stripes; tl < n_tiles; tl += n_stripes) {
+      const int64_t q = tl * kLdsProgBlock + t;
+      // (the quads belong to ONE trip: declared outside the loop they would be carried round it — 8 registers per column —
+      // for the lanes behind the fragment's end, which load nothing)
+      RawQ cq[NC], fq[NFA], kq[NK];
+#pragma unroll
+      for (int k = 0; k < NC; ++k) cq[k].lo = cq[k].hi = v4i32{0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < NFA; ++k) fq[k].lo = fq[k].hi = v4i32{0, 0, 0, 0};
+#pragma unroll
+      for (int g = 0; g < NK; ++g) kq[g].lo = kq[g].hi = v4i32{0, 0, 0, 0};
+      // every load of a step is issued before the first value is looked at
+      if (q < nq) {
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+          if (k < a.n_cols) load_rawq(cbase[k], q, a.col_w8[k] != 0, cq[k]);
+#pragma unroll
+        for (int k = 0; k < NF; ++k)
+          if (k < a.n_own) load_rawq_w(fbase[k], q, flt_width(a.own_type[k]), fq[k]);
+#pragma unroll
+        for (int g = 0; g < NK; ++g)
+          if (kbase[g]) load_rawq(kbase[g], q, l.key_type[g] != MI355Q_INT32, kq[g]);
+      } else if (q < nq_all) {  // (one lane per fragment)
+        const int left = (int)(n & 3);
+        auto gather = [&](const int8_t* base, int width, RawQ& r) {
+          int64_t v[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int64_t pos = (nq << 2) + (i < left ? i : left - 1);
+            v[i] = width == 8 ? load_one<int64_t>(base, pos) : width == 4 ? (int64_t)load_one<int32_t>(base, pos) : (int64_t)load_one<int8_t>(base, pos);
+          }
+          if (width == 8) {
+            r.lo.x = (int)(uint32_t)v[0]; r.lo.y = (int)(uint32_t)((uint64_t)v[0] >> 32); r.lo.z = (int)(uint32_t)v[1]; r.lo.w = (int)(uint32_t)((uint64_t)v[1] >> 32);
+            r.hi.x = (int)(uint32_t)v[2]; r.hi.y = (int)(uint32_t)((uint64_t)v[2] >> 32); r.hi.z = (int)(uint32_t)v[3]; r.hi.w = (int)(uint32_t)((uint64_t)v[3] >> 32);
+          } else if (width == 4) {
+            r.lo.x = (int)v[0]; r.lo.y = (int)v[1]; r.lo.z = (int)v[2]; r.lo.w = (int)v[3];
+          } else {
+            r.lo.x = (int)(((uint32_t)v[0] & 255u) | (((uint32_t)v[1] & 255u) << 8) | (((uint32_t)v[2] & 255u) << 16) | (((uint32_t)v[3] & 255u) << 24));
+          }
+        };
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+          if (k < a.n_cols) gather(cbase[k], a.col_w8[k] ? 8 : 4, cq[k]);
+#pragma unroll
+        for (int k = 0; k < NF; ++k)
+          if (k < a.n_own) gather(fbase[k], flt_width(a.own_type[k]), fq[k]);
+#pragma unroll
+        for (int g = 0; g < NK; ++g)
+          if (kbase[g]) gather(kbase[g], l.key_type[g] == MI355Q_INT32 ? 4 : 8, kq[g]);
+      }
+      const uint32_t valid = q < nq ? 15u : q < nq_all ? (1u << (int)(n & 3)) - 1u : 0u;
+      quad_rows(cq, fq, kq, valid);
+    }
+  }
+  if (bad) atomicCAS(d_err, 0, MI355Q_ERR_OUT_OF_SLOTS);
+  if (err) atomicCAS(d_err, 0, err);
+  __syncthreads();
+  if (!lds_fold_replicas<NV, kLdsProgBlock>(smem, l, t, s_full, d_err)) return;
+  lds_flush_replica0<NK, NV, kLdsProgBlock>(smem, l, p, e_lo, t, out, d_err);
+}
+
 bool make_lds_args(const DevPlan& p, const FragView& fv, int n_cus, LdsArgs* out) {
   LdsArgs& a = *out;
   bool need[kLdsVals][4] = {};
   if (!lds_describe(p, fv, 65536, tune_knobs().flags, &a, need, true)) return false;
-  // one replica: 8-byte arrays first, then the 4-byte counters
-  auto lay_out = [&](uint32_t entries) -> uint32_t {
-    uint32_t off = 0;
-    a.entries = entries;
-    a.off_keys = -1;
-    if (a.baseline) {
-      a.off_keys = (int32_t)off;
-      off += entries * 8;
-    }
-    for (int c = 0; c < a.n_vals; ++c)
-      for (int k = 1; k < 4; ++k) {
-        int32_t& o = k == 1 ? a.v[c].off_sum : k == 2 ? a.v[c].off_min : a.v[c].off_max;
-        o = -1;
-        if (need[c][k]) {
-          o = (int32_t)off;
-          off += entries * 8;
-        }
-      }
-    a.off_rows = (int32_t)off;
-    off += entries * 4;
-    for (int c = 0; c < a.n_vals; ++c) {
-      a.v[c].off_cnt = -1;
-      if (need[c][0]) {
-        a.v[c].off_cnt = (int32_t)off;
-        off += entries * 4;
-      }
-    }
-    return (off + 15u) & ~15u;
-  };
+  auto lay_out = [&](uint32_t entries) -> uint32_t { return lds_lay_out(a, need, entries); };  // (lds_args.h)
   // typed member (k_groupby_lds_typed): up to three plain INT32 filter columns, 1 - 3 plain INT32 value columns; perfect hash over INT32 keys whose
   // ranges keep the index arithmetic in 32 bits, or a baseline table over one BIGINT / DOUBLE / FLOAT / INT key
   // (no value column at all — COUNT(*) alone — is typed only under a filter: the unfiltered count shapes have members of
@@ -1256,6 +1611,60 @@ hipError_t launch_lds_groupby(const DevPlan& p, const FragView& fv, int64_t* out
   else if (a.n_flt <= 1 && a.n_keys == 1) MQ_LDS_LAUNCH(1, 1, 3, 1);                     // MultiStep, one key
   else MQ_LDS_LAUNCH(kLdsGenericFlt, 3, 3, 1);
 #undef MQ_LDS_LAUNCH
+  rec(st->k_stop, s);
+  return hipGetLastError();
+}
+
+bool lds_groupby_prog_eligible(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int n_cus) {
+  LdsProgArgs a;
+  return make_lds_prog_args(p, ap, fv, n_cus, tune_knobs().flags, &a);
+}
+
+hipError_t launch_lds_groupby_prog(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int64_t* out, int32_t* d_err,
+                                   int n_cus, hipStream_t s, LaunchStats* st) {
+  LdsProgArgs a;
+  if (!make_lds_prog_args(p, ap, fv, n_cus, tune_knobs().flags, &a)) return hipErrorInvalidValue;
+  LdsArgs& l = a.l;
+  const size_t lds = ((size_t)l.copy_bytes << l.copies_lg) + 16;
+  int64_t want = ((fv.total_rows + 3) / 4 + kLdsProgBlock - 1) / kLdsProgBlock;
+  if (want < 1) want = 1;
+  // windows: T workgroups (one per window) share a row stripe; on a full device the T of a stripe sit on one XCD
+  // (launch_lds_groupby)
+  const int T = (int)l.windows;
+  int64_t stripes = n_cus / T;
+  if (stripes > want) stripes = want;
+  if (stripes < 1) stripes = 1;
+  int grid = (int)stripes * T;
+  l.xcd_aware = 0;
+  if (T > 1 && n_cus >= 64 && (n_cus / 8) / T >= 1 && stripes * T >= n_cus - T) {
+    grid = 8 * T * ((n_cus / 8) / T);
+    l.xcd_aware = 1;
+  }
+  st->kernel_name = "k_groupby_lds_prog";
+  st->n_launches = 1;
+  st->variant = T > 1 ? 7 : 6;  // 7: the windowed form
+  rec(st->k_start, s);
+  // the smallest member that holds the step: (operand columns, filter-only columns) x (key columns, arguments)
+  const bool table1 = l.n_keys <= 1 && a.n_args <= 1;
+#define MQ_LDS_PROG_LAUNCH(NC, NF, NK, NV)                                                                              \
+  do {                                                                                                                  \
+    auto k = k_groupby_lds_prog<NC, NF, NK, NV>;                                                                        \
+    const hipError_t ea = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
+    if (ea != hipSuccess) return ea;                                                                                    \
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kLdsProgBlock), lds, s, fv.d_cols, fv.d_num_rows, fv.n_frags, fv.n_cols, a, \
+                       p, out, d_err);                                                                                  \
+  } while (0)
+  if (a.n_cols <= 2 && a.n_own == 0) {
+    if (table1) MQ_LDS_PROG_LAUNCH(2, 0, 1, 1);
+    else MQ_LDS_PROG_LAUNCH(2, 0, 3, 3);
+  } else if (a.n_cols <= 2) {
+    if (table1) MQ_LDS_PROG_LAUNCH(2, 2, 1, 1);
+    else MQ_LDS_PROG_LAUNCH(2, 2, 3, 3);
+  } else {
+    if (table1) MQ_LDS_PROG_LAUNCH(4, 2, 1, 1);
+    else MQ_LDS_PROG_LAUNCH(4, 2, 3, 3);
+  }
+#undef MQ_LDS_PROG_LAUNCH
   rec(st->k_stop, s);
   return hipGetLastError();
 }

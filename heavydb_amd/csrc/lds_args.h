@@ -6,6 +6,7 @@
 
 #include "boolfilter.h"
 #include "fast_common.h"
+#include "regprog.h"
 
 namespace mq {
 
@@ -17,6 +18,7 @@ constexpr int kLdsGenericFlt = 4;        // filter columns of the run-time-role 
 constexpr uint32_t kLdsHashSmall = 256;  // slots of one baseline replica, first attempt (many replicas)
 constexpr uint32_t kLdsHashMax = 4096;   // ... at most, second attempt
 constexpr uint32_t kLdsMaxWindows = 8;   // windows of a table that does not fit one LDS (the columns are read once per window)
+constexpr size_t kLdsBudget = 152 * 1024;  // dynamic LDS of one workgroup (one workgroup per CU): replicas + the "full" word
 
 struct LdsVal {
   int32_t col, type, nullable;           // type: MI355Q_INT32 / _INT64 / _DOUBLE (plain)
@@ -51,8 +53,11 @@ struct LdsArgs {
 // with their ranges; baseline: one 8-byte-wide key), value columns and the accumulators the targets need of each
 // (need[c] = {non-NULL count, sum, min, max}).  Perfect-hash tables of more than `max_entries` entries are refused.
 // allow_int8_flt: the caller's kernels load 1-byte filter columns (kernels_lds.hip)
+// vals_in_table = false: `p` is a plan over LOWERED columns (expression k is column n_cols + k, which the physical column
+// table `fv` does not hold): the value columns' chunks are not looked at here — the caller checks the columns its kernel
+// really reads (make_lds_prog_args)
 inline bool lds_describe(const DevPlan& p, const FragView& fv, int64_t max_entries, uint32_t knob_flags, LdsArgs* out,
-                         bool (&need)[kLdsVals][4], bool allow_int8_flt = false) {
+                         bool (&need)[kLdsVals][4], bool allow_int8_flt = false, bool vals_in_table = true) {
   LdsArgs& a = *out;
   std::memset(&a, 0, sizeof(a));
   a.windows = 1;
@@ -140,7 +145,7 @@ inline bool lds_describe(const DevPlan& p, const FragView& fv, int64_t max_entri
     for (int k = 0; k < a.n_vals; ++k)
       if (a.v[k].col == t.col) c = k;
     if (c < 0) {
-      if (a.n_vals >= kLdsVals || !all_aligned16(fv, t.col)) return false;
+      if (a.n_vals >= kLdsVals || (vals_in_table && !all_aligned16(fv, t.col))) return false;
       c = a.n_vals++;
       a.v[c].col = t.col;
       a.v[c].type = t.arg_type;
@@ -154,6 +159,156 @@ inline bool lds_describe(const DevPlan& p, const FragView& fv, int64_t max_entri
     if (t.agg == MI355Q_MIN) need[c][2] = true;
     if (t.agg == MI355Q_MAX) need[c][3] = true;
   }
+  return true;
+}
+
+// one replica of the run-time-role members (k_groupby_lds, k_groupby_lds_prog): 8-byte arrays first — keys (baseline), then
+// per value column sum / min / max as needed — then the 4-byte counters: rows, per value column the non-NULL count.
+// Sets the offsets for `entries` entries and returns the replica's bytes (a 16-byte multiple).
+inline uint32_t lds_lay_out(LdsArgs& a, const bool (&need)[kLdsVals][4], uint32_t entries) {
+  uint32_t off = 0;
+  a.entries = entries;
+  a.off_keys = -1;
+  if (a.baseline) {
+    a.off_keys = (int32_t)off;
+    off += entries * 8;
+  }
+  for (int c = 0; c < a.n_vals; ++c)
+    for (int k = 1; k < 4; ++k) {
+      int32_t& o = k == 1 ? a.v[c].off_sum : k == 2 ? a.v[c].off_min : a.v[c].off_max;
+      o = -1;
+      if (need[c][k]) {
+        o = (int32_t)off;
+        off += entries * 8;
+      }
+    }
+  a.off_rows = (int32_t)off;
+  off += entries * 4;
+  for (int c = 0; c < a.n_vals; ++c) {
+    a.v[c].off_cnt = -1;
+    if (need[c][0]) {
+      a.v[c].off_cnt = (int32_t)off;
+      off += entries * 4;
+    }
+  }
+  return (off + 15u) & ~15u;
+}
+
+// ---- k_groupby_lds_prog (kernels_lds.hip): the few-groups table around aggregate ARGUMENTS that are two-register programs
+// (regprog.h AggProgArgs), evaluated on the values the kernel has loaded.  512-lane workgroups, one per CU.
+constexpr int kLdsProgBlock = 512;
+constexpr int kLdsProgOwnFlt = 2;  // columns read for a qual alone
+// columns under range quals, after two quals on one column have become one range.  (Eight — every qual of a plan on a column
+// of its own — is what the argument struct could carry; the widest member then holds more uniform state than it has scalar
+// registers for and the spill reaches scratch, 12 bytes per lane.  Four, as k_scan_agg_prog has, compiles without.)
+constexpr int kLdsProgFlt = 4;
+// flt_src: where a range qual finds its value
+enum : int32_t { LPS_OPERAND = 0 /* + operand slot */, LPS_KEY = 4 /* + key g */, LPS_OWN = 8 /* + filter-only column k */ };
+struct LdsProgArgs {
+  LdsArgs l;  // the table side: keys, replica layout, windows; v[] in ARGUMENT order; flt[] / flt_type[]: the merged range quals
+  int32_t n_cols, n_args, n_progs, n_own;
+  int32_t col[kApMaxCols], col_w8[kApMaxCols];  // operand slots: index in the column table, 8-byte values (else 4)
+  int32_t arg_slot[kLdsVals];                   // a plain-column argument's operand slot
+  int32_t key_slot[kLdsKeys];                   // the operand slot that holds key g's column; -1: the key is loaded on its own
+  int32_t flt_src[MI355Q_MAX_QUALS];            // LPS_*
+  int32_t own_col[kLdsProgOwnFlt], own_type[kLdsProgOwnFlt];  // MI355Q_INT32 / _INT64 / _INT8 (one word per quad)
+  RegProg prog[kLdsVals];
+};
+
+// The kernel's arguments from the plan over the LOWERED columns (keys, quals, targets) + the arguments' description; false:
+// not this member.  Nothing past the physical column table is indexed: the alignment of every chunk the kernel reads —
+// operand, key and filter-only columns — is checked here, on the columns themselves.
+inline bool make_lds_prog_args(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int n_cus, uint32_t knob_flags,
+                               LdsProgArgs* out) {
+  LdsProgArgs& a = *out;
+  std::memset(&a, 0, sizeof(a));
+  if (p.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || p.bf_active || p.n_quals > MI355Q_MAX_QUALS || p.n_group < 1 ||
+      p.n_group > kLdsKeys || ap.n_args < 1 || ap.n_args > kLdsVals || ap.n_cols < 1 || ap.n_cols > kApMaxCols)
+    return false;
+  for (int g = 0; g < p.n_group; ++g)  // (an expression key is a lowered column: not this member's)
+    if (p.group_cols[g] < 0 || p.group_cols[g] >= fv.n_cols) return false;
+  for (int i = 0; i < p.n_quals; ++i)
+    if (p.quals[i].col < 0 || p.quals[i].col >= fv.n_cols) return false;
+  bool need[kLdsVals][4] = {};
+  LdsArgs& l = a.l;
+  if (!lds_describe(p, fv, 65536, knob_flags, &l, need, true, /*vals_in_table=*/false)) return false;
+  if (l.baseline || l.bf_on || l.n_vals != ap.n_args || l.n_flt > kLdsProgFlt) return false;
+  // value columns in ARGUMENT order (programs first): v[c] is argument c
+  {
+    LdsVal v2[kLdsVals];
+    bool need2[kLdsVals][4];
+    int to_arg[kLdsVals];
+    for (int c = 0; c < l.n_vals; ++c) {
+      int k = -1;
+      for (int j = 0; j < ap.n_args; ++j)
+        if (ap.arg_col[j] == l.v[c].col) k = j;
+      if (k < 0 || ap.arg_type[k] != l.v[c].type || ap.arg_nullable[k] != l.v[c].nullable) return false;
+      to_arg[c] = k;
+      v2[k] = l.v[c];
+      for (int j = 0; j < 4; ++j) need2[k][j] = need[c][j];
+    }
+    for (int c = 0; c < l.n_vals; ++c) {
+      l.v[c] = v2[c];
+      for (int j = 0; j < 4; ++j) need[c][j] = need2[c][j];
+    }
+    for (int i = 0; i < p.n_targets; ++i)
+      if (l.target_v[i] >= 0) l.target_v[i] = to_arg[l.target_v[i]];
+  }
+  a.n_cols = ap.n_cols;
+  a.n_args = ap.n_args;
+  a.n_progs = ap.n_progs;
+  for (int k = 0; k < ap.n_cols; ++k) {
+    if (!rp_type_ok(ap.col_type[k]) || ap.col[k] < 0 || ap.col[k] >= fv.n_cols || !all_aligned16(fv, ap.col[k])) return false;
+    a.col[k] = ap.col[k];
+    a.col_w8[k] = ap.col_type[k] == MI355Q_INT32 ? 0 : 1;
+  }
+  for (int c = 0; c < ap.n_args; ++c) {
+    a.arg_slot[c] = c < ap.n_progs ? 0 : ap.arg_slot[c];
+    a.prog[c] = ap.prog[c];
+  }
+  // a key column that is also an operand column is loaded once
+  for (int g = 0; g < l.n_keys; ++g) {
+    a.key_slot[g] = -1;
+    for (int k = 0; k < ap.n_cols; ++k)
+      if (ap.col[k] == l.key_col[g] && ap.col_type[k] == l.key_type[g]) a.key_slot[g] = k;
+  }
+  // a range qual tests a value already loaded where its column is an operand or key column
+  for (int i = 0; i < l.n_flt; ++i) {
+    int src = -1;
+    for (int k = 0; k < ap.n_cols; ++k)
+      if (ap.col[k] == l.flt[i].col && ap.col_type[k] == l.flt_type[i]) src = LPS_OPERAND + k;
+    for (int g = 0; g < l.n_keys && src < 0; ++g)
+      if (l.key_col[g] == l.flt[i].col && l.key_type[g] == l.flt_type[i]) src = LPS_KEY + g;
+    for (int k = 0; k < a.n_own && src < 0; ++k)
+      if (a.own_col[k] == l.flt[i].col && a.own_type[k] == l.flt_type[i]) src = LPS_OWN + k;
+    if (src < 0) {
+      if (a.n_own >= kLdsProgOwnFlt) return false;
+      a.own_col[a.n_own] = l.flt[i].col;
+      a.own_type[a.n_own] = l.flt_type[i];
+      src = LPS_OWN + a.n_own++;
+    }
+    a.flt_src[i] = src;
+  }
+  // the replica layout: as many replicas as fit; a table beyond one LDS in the fewest windows whose share fits
+  l.copy_bytes = lds_lay_out(l, need, l.entries);
+  if (l.copy_bytes > kLdsBudget) {
+    const uint32_t total = (uint32_t)p.entry_count;
+    for (uint32_t T = 2; T <= kLdsMaxWindows; ++T) {
+      const uint32_t share = (total + T - 1) / T;
+      if (lds_lay_out(l, need, share) <= kLdsBudget) {
+        l.windows = T;
+        l.copy_bytes = lds_lay_out(l, need, share);
+        break;
+      }
+    }
+    if (l.windows == 1) return false;
+  }
+  l.copies_lg = 0;
+  while (l.copies_lg < 6 && ((size_t)l.copy_bytes << (l.copies_lg + 1)) <= kLdsBudget) ++l.copies_lg;
+  // the per-entry counters are 32 bits wide per workgroup: a stripe stays below 2^32 rows (as make_lds_args)
+  int64_t stripes = (n_cus > 0 ? n_cus : 1) / (int64_t)l.windows;
+  if (stripes < 1) stripes = 1;
+  if (fv.total_rows / stripes >= 0xfff00000ll) return false;
   return true;
 }
 

@@ -16,8 +16,8 @@
 //     evaluation order of the checks) stated once, in expr.h.
 // Consumers: the atoms of a filter compiled at plan time (boolfilter.h: an atom is then the BOOLEAN such a program leaves;
 // evaluated by the row-mask pre-pass, kernels_filter.hip), the typed expression targets of the Projection family
-// (kernels_proj.hip k_proj_fast), the arguments of non-grouped aggregates (AggProgArgs below; evaluated by the scan itself,
-// kernels_filter.hip k_scan_agg_prog).
+// (kernels_proj.hip k_proj_fast), the arguments of aggregates (AggProgArgs below; evaluated by the scan itself: non-grouped
+// steps in kernels_filter.hip k_scan_agg_prog, few-groups GROUP BY steps in kernels_lds.hip k_groupby_lds_prog).
 // Programs that do not fit (CASE, more than two live values, INT8 / INT16 / FLOAT arithmetic, encoded columns, values of
 // earlier expressions) keep the interpreter (expr.h eval_expr_rows).
 #pragma once
@@ -161,8 +161,8 @@ inline bool rp_compile(const DevExpr& e, int first, int last, int n_phys_cols, S
 // (k_project, then the plain-column step); a consumer that takes this description evaluates the same thing in registers.
 // The arguments are the distinct columns the targets aggregate: the expressions first (argument k < n_progs is prog[k],
 // expression k of the plan), then plain unencoded INT32 / INT64 / DOUBLE columns.  Together they read at most kApMaxCols
-// physical columns, the consumer's operand slots.  Nothing in it is about WHERE the aggregates go: a grouped family can
-// take it as it is.
+// physical columns, the consumer's operand slots.  Nothing in it is about WHERE the aggregates go: a grouped family takes
+// it as it is (lds_args.h make_lds_prog_args; a grouped plan's PROJECT_KEY targets are passed over here).
 constexpr int kApMaxArgs = 4, kApMaxCols = 4;
 struct AggProgArgs {
   int32_t n_cols, n_args, n_progs, pad_;
@@ -181,9 +181,11 @@ inline bool agg_prog_args_of(const DevPlan& d, const DevExprSet& xs, AggProgArgs
   AggProgArgs& a = *out;
   a = AggProgArgs{};
   const int n_phys = xs.n_cols;
+  const bool grouped = d.desc_type != MI355Q_NON_GROUPED_AGGREGATE;
   for (int i = 0; i < d.n_targets; ++i) {
     const DevTarget& t = d.targets[i];
     a.target_arg[i] = -1;
+    if (grouped && t.agg == MI355Q_PROJECT_KEY) continue;  // (a grouped plan's key projections are the table's business)
     if (t.table != 0 || t.arg_f32) return false;
     if (t.agg == MI355Q_COUNT && t.col < 0) continue;
     if (t.agg != MI355Q_COUNT && t.agg != MI355Q_SUM && t.agg != MI355Q_MIN && t.agg != MI355Q_MAX && t.agg != MI355Q_AVG) return false;
@@ -200,7 +202,7 @@ inline bool agg_prog_args_of(const DevPlan& d, const DevExprSet& xs, AggProgArgs
     int type = 0, nullable = 0, n = 0;
     for (int i = 0; i < d.n_targets; ++i) {
       const DevTarget& t = d.targets[i];
-      if (t.col != col || (t.agg == MI355Q_COUNT && t.col < 0)) continue;
+      if (t.col != col || (t.agg == MI355Q_COUNT && t.col < 0) || (grouped && t.agg == MI355Q_PROJECT_KEY)) continue;
       if (n && (type != t.arg_type || nullable != t.skip_null)) return false;  // one column, two NULL conventions
       type = t.arg_type;
       nullable = t.skip_null;
@@ -223,7 +225,7 @@ inline bool agg_prog_args_of(const DevPlan& d, const DevExprSet& xs, AggProgArgs
   }
   for (int i = 0; i < d.n_targets; ++i) {
     const DevTarget& t = d.targets[i];
-    if (t.col < 0 || t.col >= n_phys || a.target_arg[i] >= 0) continue;
+    if (t.col < 0 || t.col >= n_phys || a.target_arg[i] >= 0 || (grouped && t.agg == MI355Q_PROJECT_KEY)) continue;
     if (!add_arg(t.col)) return false;
     const int slot = slot_of(t.col);
     if (slot < 0) return false;

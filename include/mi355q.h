@@ -575,6 +575,11 @@ typedef struct mi355q_exec_options {
                                             plain-column step even where the arguments compile into two-register programs
                                             that k_scan_agg_prog evaluates in registers (tests and tools/agg_prog_bench.py
                                             compare the two) */
+#define MI355Q_OPT_NO_GROUPED_AGG_PROGRAMS 8192u /* few-groups GROUP BY over aggregates of expressions: the interpreter pass
+                                            (k_project) and a plain-column grouped step even where kernel_variant 2 would
+                                            have k_groupby_lds_prog evaluate the arguments' programs beside its LDS table
+                                            (that kernel is no default: it lost to the two passes when measured; tests and
+                                            tools/agg_prog_bench.py --group compare the two) */
 
 /* per-call timing/selection report (what launchGpuCode logs,
  * QueryExecutionContext.cpp:334,364,579) */
@@ -585,6 +590,7 @@ typedef struct mi355q_exec_report {
   float total_ms;       /* HIP-event time of the whole call on the launch stream */
   int32_t n_launches;   /* launches of the dominant kernel */
   int32_t variant;      /* member of the family that ran (informational; e.g. k_groupby_lds: 4 run-time roles, 5 typed;
+                           k_groupby_lds_prog: 6 one LDS window, 7 several;
                            k_idx_scatter: 6 plain records, 7 / 8 the packed 4- / 2-byte word; k_proj_compact: 0 the fast
                            member, 1 / 2 the general member and the one-to-many member without expressions, 16 the split
                            route, 32 / 33 the one-to-many member with expressions — evaluator in LDS / row at a time) */

@@ -718,11 +718,7 @@ struct StepEvents {
 };
 int32_t step_events(DeviceCtx& ctx, StepEvents* ev, LaunchStats* st) {
   constexpr int kEvPool = 128;
-  while ((int)ctx.events.size() < kEvPool + 4) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreate(&e));
-    ctx.events.push_back(e);
-  }
+  if (int32_t e = grow_events(ctx, kEvPool + 4)) return e;
   ev->start = ctx.events[0];
   ev->stop = ctx.events[1];
   st->k_start = ctx.events[2];
@@ -806,18 +802,6 @@ mi355q_exec_options retry_options(int32_t code, mi355q_exec_options o) {
                                                             : MI355Q_OPT_NO_LDS_BASELINE;
   return o;
 }
-
-// The upload reads the SHARED pinned block: a return that does not reach finish_step (an allocation that fails, a HIP
-// error, kNotTaken) must not leave it in flight — the next call on another stream rewrites h_meta and ctx.meta while
-// the stale copy could still land.  Disarmed where the step synchronises itself or stays in flight by
-// design (mi355q_execute_async: the next call drains it first).
-struct UploadGuard {
-  hipStream_t s;
-  bool armed;
-  ~UploadGuard() {
-    if (armed) (void)hipStreamSynchronize(s);
-  }
-};
 
 }  // namespace
 
@@ -929,11 +913,7 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
   ResultPtr owned(res);
   const int nf = in->n_frags, nc = plan->n_cols;
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
+  if ((e = frag_row_totals(*in, &total_rows, &max_frag_rows))) return e;
   DeviceCtx& ctx = ctx_of(in->device_id);
   std::lock_guard<std::recursive_mutex> ctx_lock(ctx.mu);
   FragTable ft;  // (reserve / explain launch nothing: no upload to leave in flight)

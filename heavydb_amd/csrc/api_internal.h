@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -188,7 +189,38 @@ enum class FragUpload {
   kNone,            // execute_impl in RESERVE mode: lay out only, nothing is launched
 };
 int32_t upload_frag_table(DeviceCtx& ctx, const mi355q_inputs& in, int nc, void* callers_stream, FragUpload mode, FragTable* ft);
+// The upload reads the SHARED pinned block: a return that does not reach the step's own synchronisation (an allocation
+// that fails, a HIP error, kNotTaken) must not leave it in flight — the next call on another stream rewrites h_meta and
+// ctx.meta while the stale copy could still land.  Disarmed where the step synchronises itself or stays in
+// flight by design (mi355q_execute_async: the next call drains it first).
+struct UploadGuard {
+  hipStream_t s;
+  bool armed;
+  ~UploadGuard() {
+    if (armed) (void)hipStreamSynchronize(s);
+  }
+};
 
+// the rows of a step's fragments: all of them and the largest fragment's (MI355Q_ERR_INVALID_PLAN: a negative count)
+inline int32_t frag_row_totals(const mi355q_inputs& in, int64_t* total_rows, int64_t* max_frag_rows) {
+  *total_rows = *max_frag_rows = 0;
+  for (int f = 0; f < in.n_frags; ++f) {
+    if (in.num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
+    *total_rows += in.num_rows[f];
+    *max_frag_rows = std::max(*max_frag_rows, in.num_rows[f]);
+  }
+  return MI355Q_OK;
+}
+
+// at least n timing events in the context's pool (ctx.mu held); who uses which index is the caller's business
+inline int32_t grow_events(DeviceCtx& ctx, int n) {
+  while ((int)ctx.events.size() < n) {
+    hipEvent_t ev;
+    HIP_TRY(hipEventCreate(&ev));
+    ctx.events.push_back(ev);
+  }
+  return MI355Q_OK;
+}
 
 // an owned result handle: freed with mi355q_result_free unless released to the caller
 struct ResultFree {
@@ -315,7 +347,8 @@ int32_t execute_cast_key(const mi355q_plan* plan, const mi355q_inputs* in, const
 // (non-grouped aggregates whose arguments compile into two-register programs: one kernel, no projection pass)
 int32_t execute_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
                              mi355q_exec_report* report, int64_t* reserved);
-// (... and the few-groups GROUP BY steps of such arguments: k_groupby_lds_prog)
+// (... and the few-groups GROUP BY steps of such arguments: k_groupby_lds_prog.  Both lower the plan with
+// lower_program_step and run through run_program_step, api_routes.cpp)
 int32_t execute_grouped_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,
                                      mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_projected(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o,

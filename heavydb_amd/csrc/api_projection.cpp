@@ -89,11 +89,7 @@ int32_t execute_projection(const mi355q_plan* plan, const mi355q_inputs* in, con
 
   const int nf = in->n_frags, nc = n_phys;
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
   const int64_t ws_need = kExprArea + projection_scratch_bytes(nf, in->num_rows);
   if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched
     route_note(d.join_col >= 0 && d.join_hash_type >= 2 && plan->n_exprs ? "k_proj_compact (one-to-many join, expressions in registers)"
@@ -135,11 +131,7 @@ int32_t execute_projection(const mi355q_plan* plan, const mi355q_inputs* in, con
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   LaunchStats st;
   if (report) {
-    while ((int)ctx.events.size() < 4) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      ctx.events.push_back(e);
-    }
+    if (int32_t e = grow_events(ctx, 4)) return e;
     ev_start = ctx.events[0];
     ev_stop = ctx.events[1];
     st.k_start = ctx.events[2];

@@ -290,11 +290,7 @@ int32_t execute_packed_multi(const mi355q_plan* plan, const mi355q_inputs* in, c
   if (!pack_spec_of(*plan, q, d, &ps)) return kNotTaken;
   const int nf = in->n_frags, nc = plan->n_cols;
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
   // small inputs: the row kernel is as fast (kernel_variant 2 asks for this path regardless, 1 for
   // the row kernel)
   if (o.kernel_variant == 1 || (o.kernel_variant != 2 && total_rows < ((int64_t)8 << 20))) return kNotTaken;
@@ -607,11 +603,7 @@ int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, co
   const int nc = plan->n_cols, nf = in->n_frags;
   const bool inner_join = plan->join_kind != MI355Q_JOIN_LEFT;
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return kNotTaken;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
+  if (frag_row_totals(*in, &total_rows, &max_frag_rows)) return kNotTaken;  // (a negative count: the plain step's to refuse)
   // (kernel_variant 2 = "the large-input members": how the tests reach this route with small tables)
   if (nf < 1 || (o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
   // a perfect-hash table of <= 64 KB is aggregated by the row kernel in a per-workgroup LDS copy (launch_generic): probe and
@@ -1268,6 +1260,93 @@ int32_t execute_shifted_args(const mi355q_plan* plan, const mi355q_inputs* in, c
   return MI355Q_OK;
 }
 
+// ---- the two program routes (execute_agg_programs, execute_grouped_agg_programs): aggregates whose arguments are evaluated
+// in the kernel's registers.  They share what they refuse, what they derive from the stated plan, and the step itself:
+// one kernel over the stated table, one error word back.  Each keeps its own conditions around these.
+
+// An expression a qual or another expression reads is evaluated for every row: the projection pass's business.  So is a
+// disjunction among the quals.
+static bool program_step_refuses(const mi355q_plan& plan) {
+  for (int i = 0; i < plan.n_quals; ++i)
+    if (MI355Q_QUAL_OR_GROUP(plan.quals[i].op) != 0) return true;
+  return expr_qual_mask(plan) != 0 || exprs_read_exprs(plan);
+}
+
+// The stated plan as a program step's kernel takes it: the lowered plan (whose targets give an argument its type and NULL
+// rule), the stated plan's layout, the device plan and the arguments' two-register programs.
+struct ProgramStep {
+  mi355q_plan lp;
+  DevExprSet xs;
+  mi355q_qmd q;
+  DevPlan d;
+  AggProgArgs ap;
+};
+// false: not a step of these routes (the layout is not `desc_type` with 8-byte slots, row-wise; an argument the form does
+// not state, regprog.h agg_prog_args_of)
+static bool lower_program_step(const mi355q_plan& plan, int32_t desc_type, ProgramStep* ps) {
+  if (lower_exprs(plan, &ps->lp, &ps->xs, true) != MI355Q_OK || qmd_init(plan, &ps->q) != MI355Q_OK) return false;
+  if (ps->q.desc_type != desc_type || ps->q.slot_width != 8 || ps->q.output_columnar) return false;
+  if (build_dev_plan(ps->lp, ps->q, &ps->d) != MI355Q_OK) return false;
+  return agg_prog_args_of(ps->d, ps->xs, &ps->ap);
+}
+
+// The step of both routes behind their eligibility checks: the fragment table up, the result initialised, ONE launch —
+// `launch`, a hipError_t(const FragView&, int64_t* buf, int32_t* d_err, hipStream_t, LaunchStats*) that is handed fv with
+// the device's column table — and d_err[0] back; a code there ends the step with no result.  The kernel's event pair is
+// the step's time as well.  RESERVE mode (mi355q_reserve_workspace / mi355q_explain) notes the route and its kernel, lays
+// the table out, creates the events and launches nothing: there are no temporary columns to reserve.
+template <class Launch>
+static int32_t run_program_step(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                                FragView fv, const char* route, const char* kernel, Launch&& launch, mi355q_result** out,
+                                mi355q_exec_report* report, int64_t* reserved) {
+  if (reserved) {
+    route_note(route);
+    route_note(kernel);
+    *reserved = 0;
+    if (t_plan_only) return MI355Q_OK;
+  }
+  RouteScope rs(in->device_id, o.stream);
+  if (rs.status) return rs.status;
+  DeviceCtx& ctx = rs.ctx;
+  // column table | row counts | error words, one upload out of pinned memory (reserve: laid out only)
+  FragTable ft;
+  if (int32_t e = upload_frag_table(ctx, *in, fv.n_cols, o.stream, reserved ? FragUpload::kNone : FragUpload::kAlways, &ft)) return e;
+  LaunchStats st;
+  if (report || reserved) {
+    if (int32_t e = grow_events(ctx, 4)) return e;
+    st.k_start = ctx.events[2];
+    st.k_stop = ctx.events[3];
+  }
+  if (reserved) return MI355Q_OK;
+  hipStream_t s = ft.s;
+  UploadGuard upload_guard{s, true};
+  mi355q_result* res = nullptr;
+  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
+  ResultPtr owned(res);
+  fv.d_cols = ft.d_cols;
+  fv.d_num_rows = ft.d_rows;
+  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
+  HIP_TRY(launch(fv, res->buf, ft.d_err, s, &st));
+  int32_t* h_ret = (int32_t*)(ctx.h_meta + ctx.meta_bytes);
+  HIP_TRY(hipMemcpyAsync(h_ret, ft.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  upload_guard.armed = false;
+  const int32_t code = h_ret[0];
+  if (report) {
+    std::memset(report, 0, sizeof(*report));
+    std::snprintf(report->kernel_name, sizeof(report->kernel_name), "%s", st.kernel_name);
+    if (hipEventElapsedTime(&report->kernel_ms, st.k_start, st.k_stop) != hipSuccess) report->kernel_ms = 0.f;
+    report->total_ms = report->kernel_ms;
+    report->n_launches = st.n_launches;
+    report->variant = st.variant;
+    report->rows_scanned = fv.total_rows;
+    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
+  }
+  if (code) return code;
+  *out = owned.release();
+  return MI355Q_OK;
+}
+
 // Non-grouped aggregates whose ARGUMENTS are expressions — SUM(a * b) WHERE c < k, TPC-H Q6's shape.  The reference compiles
 // the argument into the row function (codegenArith, ArithmeticIR.cpp:39-431) and aggregates it in the kernel's registers
 // (query_template, QueryTemplateGenerator.cpp:265-549).  Here every expression that compiles into a two-register program
@@ -1281,89 +1360,22 @@ int32_t execute_agg_programs(const mi355q_plan* plan, const mi355q_inputs* in, c
                              mi355q_exec_report* report, int64_t* reserved) {
   if (plan->n_exprs <= 0 || plan->n_group_cols != 0 || plan->join_outer_col >= 0 || plan->output_columnar_hint != 0 || o.force_generic ||
       in->n_frags <= 0 || (o.flags & MI355Q_OPT_NO_AGG_PROGRAMS) || plan->n_quals < 0 || plan->n_quals > MI355Q_MAX_QUALS ||
-      plan->n_targets < 1 || plan->n_targets > MI355Q_MAX_TARGETS)
+      plan->n_targets < 1 || plan->n_targets > MI355Q_MAX_TARGETS || program_step_refuses(*plan))
     return kNotTaken;
-  for (int i = 0; i < plan->n_quals; ++i)
-    if (MI355Q_QUAL_OR_GROUP(plan->quals[i].op) != 0) return kNotTaken;
-  // an expression a qual or another expression reads is evaluated for every row: the projection pass's business
-  if (expr_qual_mask(*plan) != 0 || exprs_read_exprs(*plan)) return kNotTaken;
-  mi355q_plan lp;
-  DevExprSet xs;
-  mi355q_qmd q;
-  DevPlan d;
-  if (lower_exprs(*plan, &lp, &xs, true) != MI355Q_OK || qmd_init(*plan, &q) != MI355Q_OK) return kNotTaken;
-  if (q.desc_type != MI355Q_NON_GROUPED_AGGREGATE || q.slot_width != 8 || q.output_columnar) return kNotTaken;
-  if (build_dev_plan(lp, q, &d) != MI355Q_OK) return kNotTaken;
-  AggProgArgs ap;
-  if (!agg_prog_args_of(d, xs, &ap)) return kNotTaken;
-  const int nf = in->n_frags, nc = plan->n_cols;
+  ProgramStep ps;
+  if (!lower_program_step(*plan, MI355Q_NON_GROUPED_AGGREGATE, &ps)) return kNotTaken;
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
-  // (the kernel reads physical columns only: the table it is handed is the stated one, nc columns per fragment)
-  FragView fv{nullptr, nullptr, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
-  if (!scan_agg_prog_eligible(d, ap, fv)) return kNotTaken;
-  if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched, and there are no temporary columns
-    route_note("aggregate arguments as register programs");
-    route_note("k_scan_agg_prog");
-    *reserved = 0;
-    if (t_plan_only) return MI355Q_OK;
-  }
-  RouteScope rs(in->device_id, o.stream);
-  if (rs.status) return rs.status;
-  DeviceCtx& ctx = rs.ctx;
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
+  // (the kernel reads physical columns only: the table it is handed is the stated one, n_cols columns per fragment)
+  FragView fv{nullptr, nullptr, in->col_buffers, in->num_rows, in->n_frags, plan->n_cols, total_rows, max_frag_rows};
+  if (!scan_agg_prog_eligible(ps.d, ps.ap, fv)) return kNotTaken;
   const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
-  // column table | row counts | error words, one upload out of pinned memory (reserve: laid out only)
-  FragTable ft;
-  if (int32_t e = upload_frag_table(ctx, *in, nc, o.stream, reserved ? FragUpload::kNone : FragUpload::kAlways, &ft)) return e;
-  LaunchStats st;
-  if (report || reserved) {
-    while ((int)ctx.events.size() < 4) {
-      hipEvent_t ev;
-      HIP_TRY(hipEventCreate(&ev));
-      ctx.events.push_back(ev);
-    }
-    st.k_start = ctx.events[2];
-    st.k_stop = ctx.events[3];
-  }
-  if (reserved) return MI355Q_OK;
-  hipStream_t s = ft.s;
-  struct UploadGuard {  // the upload reads the SHARED pinned block: no return leaves it in flight
-    hipStream_t s;
-    bool armed;
-    ~UploadGuard() {
-      if (armed) (void)hipStreamSynchronize(s);
-    }
-  } upload_guard{s, true};
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  ResultPtr owned(res);
-  fv.d_cols = ft.d_cols;
-  fv.d_num_rows = ft.d_rows;
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  HIP_TRY(launch_scan_agg_prog(d, ap, fv, res->buf, ft.d_err, n_cus, s, &st));
-  // the error a passing row raised ends the step with no result, as execute_masked treats its pre-pass's
-  int32_t* h_ret = (int32_t*)(ctx.h_meta + ctx.meta_bytes);
-  HIP_TRY(hipMemcpyAsync(h_ret, ft.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  upload_guard.armed = false;
-  const int32_t code = h_ret[0];
-  if (report) {  // a one-kernel scan step: its event pair is the step's time as well
-    std::memset(report, 0, sizeof(*report));
-    std::snprintf(report->kernel_name, sizeof(report->kernel_name), "%s", st.kernel_name);
-    if (hipEventElapsedTime(&report->kernel_ms, st.k_start, st.k_stop) != hipSuccess) report->kernel_ms = 0.f;
-    report->total_ms = report->kernel_ms;
-    report->n_launches = st.n_launches;
-    report->variant = st.variant;
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  if (code) return code;
-  *out = owned.release();
-  return MI355Q_OK;
+  // (the error a passing row raised ends the step with no result, as execute_masked treats its pre-pass's)
+  return run_program_step(plan, in, o, ps.q, fv, "aggregate arguments as register programs", "k_scan_agg_prog",
+                          [&](const FragView& dv, int64_t* buf, int32_t* d_err, hipStream_t s, LaunchStats* st) {
+                            return launch_scan_agg_prog(ps.d, ps.ap, dv, buf, d_err, n_cus, s, st);
+                          },
+                          out, report, reserved);
 }
 
 // The GROUPED half of the route above — SELECT g, SUM(a * b), COUNT(*) FROM t WHERE c < k GROUP BY g — for the few-groups
@@ -1407,91 +1419,26 @@ int32_t execute_grouped_agg_programs(const mi355q_plan* plan, const mi355q_input
                                      mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
   if (plan->n_exprs <= 0 || plan->n_group_cols < 1 || plan->n_group_cols > 3 || plan->join_outer_col >= 0 || plan->output_columnar_hint != 0 ||
       o.force_generic || in->n_frags <= 0 || (o.flags & MI355Q_OPT_NO_GROUPED_AGG_PROGRAMS) || plan->n_quals < 0 ||
-      plan->n_quals > MI355Q_MAX_QUALS || plan->n_targets < 1 || plan->n_targets > MI355Q_MAX_TARGETS || step_bool_filter())
+      plan->n_quals > MI355Q_MAX_QUALS || plan->n_targets < 1 || plan->n_targets > MI355Q_MAX_TARGETS || step_bool_filter() ||
+      program_step_refuses(*plan))
     return kNotTaken;
-  for (int i = 0; i < plan->n_quals; ++i)
-    if (MI355Q_QUAL_OR_GROUP(plan->quals[i].op) != 0) return kNotTaken;
-  // an expression a qual or another expression reads is evaluated for every row: the projection pass's business
-  if (expr_qual_mask(*plan) != 0 || exprs_read_exprs(*plan)) return kNotTaken;
-  const int nf = in->n_frags, nc = plan->n_cols;
+  // (the rows ahead of the lowering here: the size rule spares a small step the lowering)
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
   if (o.kernel_variant != 2 && total_rows < ((int64_t)1 << 20)) return kNotTaken;  // (the size rule above)
-  mi355q_plan lp;
-  DevExprSet xs;
-  mi355q_qmd q;
-  DevPlan d;
-  if (lower_exprs(*plan, &lp, &xs, true) != MI355Q_OK || qmd_init(*plan, &q) != MI355Q_OK) return kNotTaken;
-  if (q.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || q.slot_width != 8 || q.output_columnar) return kNotTaken;
-  if (build_dev_plan(lp, q, &d) != MI355Q_OK) return kNotTaken;
-  AggProgArgs ap;
-  if (!agg_prog_args_of(d, xs, &ap)) return kNotTaken;
-  if (o.kernel_variant != 2 && !grouped_prog_class_on_by_default(ap)) return kNotTaken;  // (the class rule above)
-  // (the kernel reads physical columns only: the table it is handed is the stated one, nc columns per fragment)
-  FragView fv{nullptr, nullptr, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
+  ProgramStep ps;
+  if (!lower_program_step(*plan, MI355Q_GROUP_BY_PERFECT_HASH, &ps)) return kNotTaken;
+  if (o.kernel_variant != 2 && !grouped_prog_class_on_by_default(ps.ap)) return kNotTaken;  // (the class rule above)
+  // (the kernel reads physical columns only: the table it is handed is the stated one, n_cols columns per fragment)
+  FragView fv{nullptr, nullptr, in->col_buffers, in->num_rows, in->n_frags, plan->n_cols, total_rows, max_frag_rows};
   const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
-  if (!lds_groupby_prog_eligible(d, ap, fv, n_cus)) return kNotTaken;
-  if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched, and there are no temporary columns
-    route_note("grouped aggregate arguments as register programs");
-    route_note("k_groupby_lds_prog");
-    *reserved = 0;
-    if (t_plan_only) return MI355Q_OK;
-  }
-  RouteScope rs(in->device_id, o.stream);
-  if (rs.status) return rs.status;
-  DeviceCtx& ctx = rs.ctx;
-  // column table | row counts | error words, one upload out of pinned memory (reserve: laid out only)
-  FragTable ft;
-  if (int32_t e = upload_frag_table(ctx, *in, nc, o.stream, reserved ? FragUpload::kNone : FragUpload::kAlways, &ft)) return e;
-  LaunchStats st;
-  if (report || reserved) {
-    while ((int)ctx.events.size() < 4) {
-      hipEvent_t ev;
-      HIP_TRY(hipEventCreate(&ev));
-      ctx.events.push_back(ev);
-    }
-    st.k_start = ctx.events[2];
-    st.k_stop = ctx.events[3];
-  }
-  if (reserved) return MI355Q_OK;
-  hipStream_t s = ft.s;
-  struct UploadGuard {  // the upload reads the SHARED pinned block: no return leaves it in flight
-    hipStream_t s;
-    bool armed;
-    ~UploadGuard() {
-      if (armed) (void)hipStreamSynchronize(s);
-    }
-  } upload_guard{s, true};
-  mi355q_result* res = nullptr;
-  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
-  ResultPtr owned(res);
-  fv.d_cols = ft.d_cols;
-  fv.d_num_rows = ft.d_rows;
-  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
-  HIP_TRY(launch_lds_groupby_prog(d, ap, fv, res->buf, ft.d_err, n_cus, s, &st));
-  // an error a passing row raised (7), or a key outside its declared range, ends the step with no result
-  int32_t* h_ret = (int32_t*)(ctx.h_meta + ctx.meta_bytes);
-  HIP_TRY(hipMemcpyAsync(h_ret, ft.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  upload_guard.armed = false;
-  const int32_t code = h_ret[0];
-  if (report) {  // a one-kernel step: its event pair is the step's time as well
-    std::memset(report, 0, sizeof(*report));
-    std::snprintf(report->kernel_name, sizeof(report->kernel_name), "%s", st.kernel_name);
-    if (hipEventElapsedTime(&report->kernel_ms, st.k_start, st.k_stop) != hipSuccess) report->kernel_ms = 0.f;
-    report->total_ms = report->kernel_ms;
-    report->n_launches = st.n_launches;
-    report->variant = st.variant;
-    report->rows_scanned = total_rows;
-    report->algorithmic_bytes = algorithmic_bytes(*plan, *in);
-  }
-  if (code) return code;
-  *out = owned.release();
-  return MI355Q_OK;
+  if (!lds_groupby_prog_eligible(ps.d, ps.ap, fv, n_cus)) return kNotTaken;
+  // (an error a passing row raised (7), or a key outside its declared range, ends the step with no result)
+  return run_program_step(plan, in, o, ps.q, fv, "grouped aggregate arguments as register programs", "k_groupby_lds_prog",
+                          [&](const FragView& dv, int64_t* buf, int32_t* d_err, hipStream_t s, LaunchStats* st) {
+                            return launch_lds_groupby_prog(ps.d, ps.ap, dv, buf, d_err, n_cus, s, st);
+                          },
+                          out, report, reserved);
 }
 
 // Plans with projected expressions (mi355q_expr): scan / filter / PROJECT.  The expressions of a pass of
@@ -1513,11 +1460,7 @@ int32_t execute_projected(const mi355q_plan* plan, const mi355q_inputs* in, cons
   if (nf == 0) return mi355q_execute(&lp, in, &o, out, report);
   const uint32_t qual_expr_mask = expr_qual_mask(*plan);
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
   int32_t widths[MI355Q_MAX_EXPRS];
   for (int k = 0; k < nx; ++k) widths[k] = plain_width(xs.e[k].store_type);
 
@@ -1579,11 +1522,7 @@ int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const B
   mp.quals[0].op = MI355Q_EQ;
   mp.quals[0].ival = 1;
   int64_t total_rows = 0, max_frag_rows = 0;
-  for (int f = 0; f < nf; ++f) {
-    if (in->num_rows[f] < 0) return MI355Q_ERR_INVALID_PLAN;
-    total_rows += in->num_rows[f];
-    max_frag_rows = std::max(max_frag_rows, in->num_rows[f]);
-  }
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
   if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched
     route_note("k_filter_mask (program atoms + truth table -> 1 B/row)");
     return execute_impl(&mp, in, &o, out, report, nullptr, reserved);

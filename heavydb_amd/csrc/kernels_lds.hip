@@ -181,6 +181,146 @@ MQ_D WinMap lds_window_map(uint32_t T, uint32_t xcd_aware) {
   return m;
 }
 
+// The replicated table of the run-time-role members — k_groupby_lds (kLdsBlock lanes) and k_groupby_lds_prog (kLdsProgBlock)
+// below — behind their row loops: the fold of replicas 1 .. K-1 into replica 0 and the merge of replica 0 into the output
+// table, ONE text with the workgroup's size a parameter.  The NULL-key translation, the padding of the last window, the
+// overflow protocol of a baseline table (s_full / d_err[1]) and the reduce rule per target live here and nowhere else
+// (what sharing did to the members' registers: DESIGN 3.4).  The initialisation of the replicas stays a loop in each of
+// the two kernels: as a shared function it put 20 bytes of scratch per lane into k_groupby_lds_prog<2, 0, 3, 3>, which had
+// none.  k_groupby_lds_typed keeps an epilogue of its own: its replicas are laid out by t_off_*, with INT32 min / max and MM
+// compiled in — roles these functions would have to take at run time.
+// lds_fold_replicas: false = the attempt is lost (a baseline table: the replicas together hold more groups than one does).
+template <int NV, int BLOCK>
+MQ_D bool lds_fold_replicas(char* smem, const LdsArgs& a, int t, volatile uint32_t* s_full, int32_t* d_err) {
+  // ---- fold replicas 1 .. K-1 into replica 0
+  const uint32_t K = 1u << a.copies_lg;
+  const uint32_t ne = a.entries;
+  char* const rep0 = smem;
+  for (uint32_t r = 1; r < K; ++r) {
+    char* rep = smem + (size_t)r * a.copy_bytes;
+    for (uint32_t e = t; e < ne; e += BLOCK) {
+      const uint32_t rows = ((uint32_t*)(rep + a.off_rows))[e];
+      if (!rows) continue;
+      uint32_t e0 = e;
+      if (a.baseline) {
+        const int64_t fk = ((int64_t*)(rep + a.off_keys))[e];
+        e0 = lds_key_slot((int64_t*)(rep0 + a.off_keys), ne, fk, lds_key_mix(fk));
+        if (e0 == kNoSlot) {  // the replicas together hold more groups than one does
+          if (atomicExch((uint32_t*)s_full, 1u) == 0u) atomicExch(d_err + 1, 1);
+          continue;
+        }
+      }
+      atomicAdd((uint32_t*)(rep0 + a.off_rows) + e0, rows);
+#pragma unroll
+      for (int c = 0; c < NV; ++c) {
+        if (c >= a.n_vals) break;
+        const LdsVal& v = a.v[c];
+        const bool fp = v.type == MI355Q_DOUBLE;
+        if (v.off_cnt >= 0) atomicAdd((uint32_t*)(rep0 + v.off_cnt) + e0, ((uint32_t*)(rep + v.off_cnt))[e]);
+        if (v.off_sum >= 0) {
+          if (fp) atomicAdd((double*)(rep0 + v.off_sum) + e0, ((double*)(rep + v.off_sum))[e]);
+          else atomicAdd((unsigned long long*)(rep0 + v.off_sum) + e0, ((unsigned long long*)(rep + v.off_sum))[e]);
+        }
+        if (v.off_min >= 0) {
+          if (fp) lds_min_f64((int64_t*)(rep0 + v.off_min) + e0, ((double*)(rep + v.off_min))[e]);
+          else atomicMin((long long*)(rep0 + v.off_min) + e0, ((long long*)(rep + v.off_min))[e]);
+        }
+        if (v.off_max >= 0) {
+          if (fp) lds_max_f64((int64_t*)(rep0 + v.off_max) + e0, ((double*)(rep + v.off_max))[e]);
+          else atomicMax((long long*)(rep0 + v.off_max) + e0, ((long long*)(rep + v.off_max))[e]);
+        }
+      }
+    }
+    __syncthreads();  // (baseline: inserts into replica 0 of one round must be visible to the next)
+    if (*s_full) return false;
+  }
+  return true;
+}
+// e_lo: the first entry index of the workgroup's window (perfect hash)
+template <int NK, int NV, int BLOCK>
+MQ_D void lds_flush_replica0(char* rep0, const LdsArgs& a, const DevPlan& p, uint32_t e_lo, int t, int64_t* out, int32_t* d_err) {
+  const uint32_t ne = a.entries;
+  // ---- merge every live entry of replica 0 into the output table with the reduce rule
+  for (uint32_t e = t; e < ne; e += BLOCK) {
+    const uint32_t rows = ((const uint32_t*)(rep0 + a.off_rows))[e];
+    if (!rows) continue;
+    int64_t key0 = 0, key1 = 0, key2 = 0;  // the group columns' values as decoded (what a projection shows)
+    int64_t* slots;
+    if (a.baseline) {
+      key0 = ((const int64_t*)(rep0 + a.off_keys))[e];
+      slots = baseline_find_or_insert(out, (uint32_t)p.entry_count, p.row_quad, p.key_width, key0);
+      if (!slots) {
+        atomicCAS(d_err, 0, -1);  // out of group slots: the caller grows the table and retries
+        continue;
+      }
+    } else {
+      int64_t tk0 = 0, tk1 = 0, tk2 = 0;
+      if ((uint64_t)e_lo + e >= (uint64_t)p.entry_count) continue;  // (padding of the last window)
+      uint32_t rem = e_lo + e;
+#pragma unroll
+      for (int g = NK - 1; g >= 0; --g) {  // entry index -> key components (mul_g ascending with g)
+        if (g >= a.n_keys) continue;
+        const int64_t d = (int64_t)(rem / (uint32_t)a.key_mul[g]);
+        rem -= (uint32_t)(d * a.key_mul[g]);
+        const int64_t tk = d + a.key_min[g];
+        const int64_t orig = (a.key_translate[g] && tk == a.key_null_key[g])
+                                 ? (a.key_type[g] == MI355Q_INT32 ? (int64_t)INT32_MIN : INT64_MIN) : tk;
+        if (g == 0) { tk0 = tk; key0 = orig; } else if (g == 1) { tk1 = tk; key1 = orig; } else { tk2 = tk; key2 = orig; }
+      }
+      int64_t* row = out + (size_t)(e_lo + e) * p.row_quad;
+      if (!p.keyless) {
+        if (MQ_LOAD64(row) == kEmptyKey64) {
+          if (a.n_keys > 2) MQ_STORE64(row + 2, tk2);
+          if (a.n_keys > 1) MQ_STORE64(row + 1, tk1);
+          MQ_STORE64(row, tk0);
+        }
+        slots = row + a.n_keys;
+      } else {
+        slots = row;
+      }
+    }
+    // the entry's partial row, slot by slot (static slot indices: no private-memory array), merged with the reduce rule
+#pragma unroll
+    for (int i = 0; i < MI355Q_MAX_TARGETS; ++i) {
+      if (i >= p.n_targets) break;
+      const DevTarget& tg = p.targets[i];
+      if (tg.slot < 0) continue;
+      int64_t v0 = p.init_vals[tg.slot], v1 = tg.agg == MI355Q_AVG ? p.init_vals[tg.slot + 1] : 0;
+      if (tg.agg == MI355Q_PROJECT_KEY) {
+        v0 = tg.key_idx == 0 ? key0 : tg.key_idx == 1 ? key1 : key2;
+      } else {
+        const int c = a.target_v[i];
+        if (c < 0) {
+          v0 = (int64_t)rows;
+        } else {
+          const LdsVal v = c == 0 ? a.v[0] : (NV > 1 && c == 1) ? a.v[NV > 1 ? 1 : 0] : a.v[NV > 2 ? 2 : 0];
+          // rows with a value: the non-NULL counter where one is kept (nullable column), else every row
+          const uint32_t cnt = v.off_cnt >= 0 ? ((const uint32_t*)(rep0 + v.off_cnt))[e] : rows;
+          switch (tg.agg) {
+            case MI355Q_COUNT: v0 = (int64_t)cnt; break;
+            case MI355Q_AVG:
+              v1 = (int64_t)cnt;
+              [[fallthrough]];
+            case MI355Q_SUM:
+              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_sum))[e];
+              break;
+            case MI355Q_MIN:
+              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_min))[e];
+              break;
+            default:
+              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_max))[e];
+          }
+        }
+      }
+      // reduce_target reads that_slots[t.slot (+ 1)]: hand it a two-quad window positioned at the target's slot
+      int64_t win[2] = {v0, v1};
+      DevTarget lt = tg;
+      lt.slot = 0;
+      reduce_target<true>(lt, p.init_vals + tg.slot, slots + tg.slot, win);
+    }
+  }
+}
+
 // NF / NK / NV: quals, key columns and value columns this member holds registers for; UQ quads per column per step.
 // Every index into the kernel-argument structs is a compile-time constant after unrolling: a dynamically indexed
 // by-value kernel argument is lowered to a private-memory (scratch) copy, and every access to it would then be a
@@ -386,126 +526,8 @@ __global__ __launch_bounds__(kLdsBlock) void k_groupby_lds(const int8_t* const* 
   __syncthreads();
   if (*s_full) return;
 
-  // ---- fold replicas 1 .. K-1 into replica 0
-  char* const rep0 = smem;
-  for (uint32_t r = 1; r < K; ++r) {
-    char* rep = smem + (size_t)r * a.copy_bytes;
-    for (uint32_t e = t; e < ne; e += kLdsBlock) {
-      const uint32_t rows = ((uint32_t*)(rep + a.off_rows))[e];
-      if (!rows) continue;
-      uint32_t e0 = e;
-      if (a.baseline) {
-        const int64_t fk = ((int64_t*)(rep + a.off_keys))[e];
-        e0 = lds_key_slot((int64_t*)(rep0 + a.off_keys), ne, fk, lds_key_mix(fk));
-        if (e0 == kNoSlot) {  // the replicas together hold more groups than one does
-          if (atomicExch((uint32_t*)s_full, 1u) == 0u) atomicExch(d_err + 1, 1);
-          continue;
-        }
-      }
-      atomicAdd((uint32_t*)(rep0 + a.off_rows) + e0, rows);
-#pragma unroll
-      for (int c = 0; c < NV; ++c) {
-        if (c >= a.n_vals) break;
-        const LdsVal& v = a.v[c];
-        const bool fp = v.type == MI355Q_DOUBLE;
-        if (v.off_cnt >= 0) atomicAdd((uint32_t*)(rep0 + v.off_cnt) + e0, ((uint32_t*)(rep + v.off_cnt))[e]);
-        if (v.off_sum >= 0) {
-          if (fp) atomicAdd((double*)(rep0 + v.off_sum) + e0, ((double*)(rep + v.off_sum))[e]);
-          else atomicAdd((unsigned long long*)(rep0 + v.off_sum) + e0, ((unsigned long long*)(rep + v.off_sum))[e]);
-        }
-        if (v.off_min >= 0) {
-          if (fp) lds_min_f64((int64_t*)(rep0 + v.off_min) + e0, ((double*)(rep + v.off_min))[e]);
-          else atomicMin((long long*)(rep0 + v.off_min) + e0, ((long long*)(rep + v.off_min))[e]);
-        }
-        if (v.off_max >= 0) {
-          if (fp) lds_max_f64((int64_t*)(rep0 + v.off_max) + e0, ((double*)(rep + v.off_max))[e]);
-          else atomicMax((long long*)(rep0 + v.off_max) + e0, ((long long*)(rep + v.off_max))[e]);
-        }
-      }
-    }
-    __syncthreads();  // (baseline: inserts into replica 0 of one round must be visible to the next)
-    if (*s_full) return;
-  }
-
-  // ---- merge every live entry of replica 0 into the output table with the reduce rule
-  for (uint32_t e = t; e < ne; e += kLdsBlock) {
-    const uint32_t rows = ((const uint32_t*)(rep0 + a.off_rows))[e];
-    if (!rows) continue;
-    int64_t key0 = 0, key1 = 0, key2 = 0;  // the group columns' values as decoded (what a projection shows)
-    int64_t* slots;
-    if (a.baseline) {
-      key0 = ((const int64_t*)(rep0 + a.off_keys))[e];
-      slots = baseline_find_or_insert(out, (uint32_t)p.entry_count, p.row_quad, p.key_width, key0);
-      if (!slots) {
-        atomicCAS(d_err, 0, -1);  // out of group slots: the caller grows the table and retries
-        continue;
-      }
-    } else {
-      int64_t tk0 = 0, tk1 = 0, tk2 = 0;
-      if ((uint64_t)e_lo + e >= (uint64_t)p.entry_count) continue;  // (padding of the last window)
-      uint32_t rem = e_lo + e;
-#pragma unroll
-      for (int g = NK - 1; g >= 0; --g) {  // entry index -> key components (mul_g ascending with g)
-        if (g >= a.n_keys) continue;
-        const int64_t d = (int64_t)(rem / (uint32_t)a.key_mul[g]);
-        rem -= (uint32_t)(d * a.key_mul[g]);
-        const int64_t tk = d + a.key_min[g];
-        const int64_t orig = (a.key_translate[g] && tk == a.key_null_key[g])
-                                 ? (a.key_type[g] == MI355Q_INT32 ? (int64_t)INT32_MIN : INT64_MIN) : tk;
-        if (g == 0) { tk0 = tk; key0 = orig; } else if (g == 1) { tk1 = tk; key1 = orig; } else { tk2 = tk; key2 = orig; }
-      }
-      int64_t* row = out + (size_t)(e_lo + e) * p.row_quad;
-      if (!p.keyless) {
-        if (MQ_LOAD64(row) == kEmptyKey64) {
-          if (a.n_keys > 2) MQ_STORE64(row + 2, tk2);
-          if (a.n_keys > 1) MQ_STORE64(row + 1, tk1);
-          MQ_STORE64(row, tk0);
-        }
-        slots = row + a.n_keys;
-      } else {
-        slots = row;
-      }
-    }
-    // the entry's partial row, slot by slot (static slot indices: no private-memory array), merged with the reduce rule
-#pragma unroll
-    for (int i = 0; i < MI355Q_MAX_TARGETS; ++i) {
-      if (i >= p.n_targets) break;
-      const DevTarget& tg = p.targets[i];
-      if (tg.slot < 0) continue;
-      int64_t v0 = p.init_vals[tg.slot], v1 = tg.agg == MI355Q_AVG ? p.init_vals[tg.slot + 1] : 0;
-      if (tg.agg == MI355Q_PROJECT_KEY) {
-        v0 = tg.key_idx == 0 ? key0 : tg.key_idx == 1 ? key1 : key2;
-      } else {
-        const int c = a.target_v[i];
-        if (c < 0) {
-          v0 = (int64_t)rows;
-        } else {
-          const LdsVal v = c == 0 ? a.v[0] : (NV > 1 && c == 1) ? a.v[NV > 1 ? 1 : 0] : a.v[NV > 2 ? 2 : 0];
-          // rows with a value: the non-NULL counter where one is kept (nullable column), else every row
-          const uint32_t cnt = v.off_cnt >= 0 ? ((const uint32_t*)(rep0 + v.off_cnt))[e] : rows;
-          switch (tg.agg) {
-            case MI355Q_COUNT: v0 = (int64_t)cnt; break;
-            case MI355Q_AVG:
-              v1 = (int64_t)cnt;
-              [[fallthrough]];
-            case MI355Q_SUM:
-              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_sum))[e];
-              break;
-            case MI355Q_MIN:
-              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_min))[e];
-              break;
-            default:
-              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_max))[e];
-          }
-        }
-      }
-      // reduce_target reads that_slots[t.slot (+ 1)]: hand it a two-quad window positioned at the target's slot
-      int64_t win[2] = {v0, v1};
-      DevTarget lt = tg;
-      lt.slot = 0;
-      reduce_target<true>(lt, p.init_vals + tg.slot, slots + tg.slot, win);
-    }
-  }
+  if (!lds_fold_replicas<NV, kLdsBlock>(smem, a, t, s_full, d_err)) return;
+  lds_flush_replica0<NK, NV, kLdsBlock>(smem, a, p, e_lo, t, out, d_err);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1042,142 +1064,6 @@ __global__ __launch_bounds__(kLdsBlock) void k_groupby_lds_typed(const int8_t* c
   }
 }
 
-// The epilogue of k_groupby_lds_prog below: k_groupby_lds's fold of the replicas into replica 0 and its merge of replica 0
-// into the output table, as functions with the workgroup's size a parameter.  A COPY: k_groupby_lds keeps its own text —
-// calling these from it changed the register count of one of its instantiations (<1, 1, 3, 1>: 93 -> 92 VGPRs), and the
-// existing members' code objects were to stay as they are.
-// lds_fold_replicas: false = the attempt is lost (a baseline table: the replicas together hold more groups than one does).
-template <int NV, int BLOCK>
-MQ_D bool lds_fold_replicas(char* smem, const LdsArgs& a, int t, volatile uint32_t* s_full, int32_t* d_err) {
-  // ---- fold replicas 1 .. K-1 into replica 0
-  const uint32_t K = 1u << a.copies_lg;
-  const uint32_t ne = a.entries;
-  char* const rep0 = smem;
-  for (uint32_t r = 1; r < K; ++r) {
-    char* rep = smem + (size_t)r * a.copy_bytes;
-    for (uint32_t e = t; e < ne; e += BLOCK) {
-      const uint32_t rows = ((uint32_t*)(rep + a.off_rows))[e];
-      if (!rows) continue;
-      uint32_t e0 = e;
-      if (a.baseline) {
-        const int64_t fk = ((int64_t*)(rep + a.off_keys))[e];
-        e0 = lds_key_slot((int64_t*)(rep0 + a.off_keys), ne, fk, lds_key_mix(fk));
-        if (e0 == kNoSlot) {  // the replicas together hold more groups than one does
-          if (atomicExch((uint32_t*)s_full, 1u) == 0u) atomicExch(d_err + 1, 1);
-          continue;
-        }
-      }
-      atomicAdd((uint32_t*)(rep0 + a.off_rows) + e0, rows);
-#pragma unroll
-      for (int c = 0; c < NV; ++c) {
-        if (c >= a.n_vals) break;
-        const LdsVal& v = a.v[c];
-        const bool fp = v.type == MI355Q_DOUBLE;
-        if (v.off_cnt >= 0) atomicAdd((uint32_t*)(rep0 + v.off_cnt) + e0, ((uint32_t*)(rep + v.off_cnt))[e]);
-        if (v.off_sum >= 0) {
-          if (fp) atomicAdd((double*)(rep0 + v.off_sum) + e0, ((double*)(rep + v.off_sum))[e]);
-          else atomicAdd((unsigned long long*)(rep0 + v.off_sum) + e0, ((unsigned long long*)(rep + v.off_sum))[e]);
-        }
-        if (v.off_min >= 0) {
-          if (fp) lds_min_f64((int64_t*)(rep0 + v.off_min) + e0, ((double*)(rep + v.off_min))[e]);
-          else atomicMin((long long*)(rep0 + v.off_min) + e0, ((long long*)(rep + v.off_min))[e]);
-        }
-        if (v.off_max >= 0) {
-          if (fp) lds_max_f64((int64_t*)(rep0 + v.off_max) + e0, ((double*)(rep + v.off_max))[e]);
-          else atomicMax((long long*)(rep0 + v.off_max) + e0, ((long long*)(rep + v.off_max))[e]);
-        }
-      }
-    }
-    __syncthreads();  // (baseline: inserts into replica 0 of one round must be visible to the next)
-    if (*s_full) return false;
-  }
-  return true;
-}
-// e_lo: the first entry index of the workgroup's window (perfect hash)
-template <int NK, int NV, int BLOCK>
-MQ_D void lds_flush_replica0(char* rep0, const LdsArgs& a, const DevPlan& p, uint32_t e_lo, int t, int64_t* out, int32_t* d_err) {
-  const uint32_t ne = a.entries;
-  // ---- merge every live entry of replica 0 into the output table with the reduce rule
-  for (uint32_t e = t; e < ne; e += BLOCK) {
-    const uint32_t rows = ((const uint32_t*)(rep0 + a.off_rows))[e];
-    if (!rows) continue;
-    int64_t key0 = 0, key1 = 0, key2 = 0;  // the group columns' values as decoded (what a projection shows)
-    int64_t* slots;
-    if (a.baseline) {
-      key0 = ((const int64_t*)(rep0 + a.off_keys))[e];
-      slots = baseline_find_or_insert(out, (uint32_t)p.entry_count, p.row_quad, p.key_width, key0);
-      if (!slots) {
-        atomicCAS(d_err, 0, -1);  // out of group slots: the caller grows the table and retries
-        continue;
-      }
-    } else {
-      int64_t tk0 = 0, tk1 = 0, tk2 = 0;
-      if ((uint64_t)e_lo + e >= (uint64_t)p.entry_count) continue;  // (padding of the last window)
-      uint32_t rem = e_lo + e;
-#pragma unroll
-      for (int g = NK - 1; g >= 0; --g) {  // entry index -> key components (mul_g ascending with g)
-        if (g >= a.n_keys) continue;
-        const int64_t d = (int64_t)(rem / (uint32_t)a.key_mul[g]);
-        rem -= (uint32_t)(d * a.key_mul[g]);
-        const int64_t tk = d + a.key_min[g];
-        const int64_t orig = (a.key_translate[g] && tk == a.key_null_key[g])
-                                 ? (a.key_type[g] == MI355Q_INT32 ? (int64_t)INT32_MIN : INT64_MIN) : tk;
-        if (g == 0) { tk0 = tk; key0 = orig; } else if (g == 1) { tk1 = tk; key1 = orig; } else { tk2 = tk; key2 = orig; }
-      }
-      int64_t* row = out + (size_t)(e_lo + e) * p.row_quad;
-      if (!p.keyless) {
-        if (MQ_LOAD64(row) == kEmptyKey64) {
-          if (a.n_keys > 2) MQ_STORE64(row + 2, tk2);
-          if (a.n_keys > 1) MQ_STORE64(row + 1, tk1);
-          MQ_STORE64(row, tk0);
-        }
-        slots = row + a.n_keys;
-      } else {
-        slots = row;
-      }
-    }
-    // the entry's partial row, slot by slot (static slot indices: no private-memory array), merged with the reduce rule
-#pragma unroll
-    for (int i = 0; i < MI355Q_MAX_TARGETS; ++i) {
-      if (i >= p.n_targets) break;
-      const DevTarget& tg = p.targets[i];
-      if (tg.slot < 0) continue;
-      int64_t v0 = p.init_vals[tg.slot], v1 = tg.agg == MI355Q_AVG ? p.init_vals[tg.slot + 1] : 0;
-      if (tg.agg == MI355Q_PROJECT_KEY) {
-        v0 = tg.key_idx == 0 ? key0 : tg.key_idx == 1 ? key1 : key2;
-      } else {
-        const int c = a.target_v[i];
-        if (c < 0) {
-          v0 = (int64_t)rows;
-        } else {
-          const LdsVal v = c == 0 ? a.v[0] : (NV > 1 && c == 1) ? a.v[NV > 1 ? 1 : 0] : a.v[NV > 2 ? 2 : 0];
-          // rows with a value: the non-NULL counter where one is kept (nullable column), else every row
-          const uint32_t cnt = v.off_cnt >= 0 ? ((const uint32_t*)(rep0 + v.off_cnt))[e] : rows;
-          switch (tg.agg) {
-            case MI355Q_COUNT: v0 = (int64_t)cnt; break;
-            case MI355Q_AVG:
-              v1 = (int64_t)cnt;
-              [[fallthrough]];
-            case MI355Q_SUM:
-              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_sum))[e];
-              break;
-            case MI355Q_MIN:
-              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_min))[e];
-              break;
-            default:
-              if (cnt) v0 = ((const int64_t*)(rep0 + v.off_max))[e];
-          }
-        }
-      }
-      // reduce_target reads that_slots[t.slot (+ 1)]: hand it a two-quad window positioned at the target's slot
-      int64_t win[2] = {v0, v1};
-      DevTarget lt = tg;
-      lt.slot = 0;
-      reduce_target<true>(lt, p.init_vals + tg.slot, slots + tg.slot, win);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // k_groupby_lds_prog: GROUPED aggregates whose ARGUMENTS are expressions — SELECT g, SUM(a * b), COUNT(*) WHERE c < k
 // GROUP BY g — in one pass: k_groupby_lds's table (K replicas in dynamic LDS, lane l on replica l % K, lds_update, windows,
@@ -1217,7 +1103,7 @@ __global__ __launch_bounds__(kLdsProgBlock) void k_groupby_lds_prog(const int8_t
   const WinMap wm = lds_window_map(T, l.xcd_aware);
   const uint32_t stripe = wm.stripe, n_stripes = wm.n_stripes;
   const uint32_t e_lo = wm.win * ne;  // first entry index of the window
-  // ---- initialise every replica: counters 0, sums 0, min / max identities (as k_groupby_lds)
+  // ---- initialise every replica: counters 0, sums 0, min / max identities (as k_groupby_lds; its own loop: DESIGN 3.4)
   for (uint32_t r = 0; r < K; ++r) {
     char* rep = smem + (size_t)r * l.copy_bytes;
     for (uint32_t e = t; e < ne; e += kLdsProgBlock) {

@@ -210,6 +210,7 @@ OPT_NO_IDX_PACK = 1024
 OPT_NO_LATTICE_PART = 2048
 OPT_NO_AGG_PROGRAMS = 4096
 OPT_NO_GROUPED_AGG_PROGRAMS = 8192
+OPT_NO_LATTICE_PACK = 16384
 
 
 class ExecReport(C.Structure):

@@ -268,6 +268,21 @@ MQ_D bool lattice_index(const ScatterArgs& g, int64_t key, uint64_t* idx) {
   return r == 0 && q < g.lat_card;
 }
 
+// Packed records of the lattice member.  A record of partition idx mod P only needs e = idx / P, the entry inside the
+// unit, and the member runs only where a unit's entries fit its LDS table (<= 150 KB / 4 = 38 400), so e fits 16 bits by
+// the member's own precondition.  A 128-byte segment then holds twelve records instead of eight, struct-of-arrays so that
+// every value stays 8-byte aligned:
+//   bytes 0..95   int64 val[12]      bytes 96..119   uint16 e[12]      bytes 120..127   unused
+// Record i of a run lives in segment i / 12 at position i % 12; a run keeps its cap / 8 segments where they were and
+// holds up to cap / 8 x 12 records.  The flushers copy whole segments verbatim, as before.
+constexpr uint32_t kPackRecs = 12;       // records per 128-byte segment, packed
+constexpr uint32_t kPackEntryOff = 96;   // byte offset of e[12] in a segment
+// In this mode flushed[p] holds the stream position of the open line's first record instead of the line's index, so a
+// producer finds "is my line open" and its offset in the line with one subtraction; only the offset (< 12 x 64) is divided:
+// x / 12 = x * ceil(2^19 / 12) >> 19 while x * 4 / (12 x 2^19) < 1 / 12, i.e. for x < 2^17 — a 16-bit product, no
+// multiply-high on the producers' path (they are bound by the instructions they issue, not by the bytes they write)
+MQ_D uint32_t div12_small(uint32_t x) { return ((x & 0xffffu) * 43691u) >> 19; }
+
 template <typename FT, typename VT>
 struct Tile {
   Quad<FT> f;
@@ -375,7 +390,8 @@ MQ_D void spill_raw(const SpillList& sl, const ScatterArgs& g, unsigned long lon
 //   cursor[p]   stream positions handed out               (producers: atomicAdd)
 //   written[p]  records that have reached the staging area (producers: atomicAdd after the write)
 //   flushed[p]  lines already sent to the run = index of the open line (flushers: store after
-//               the line has been read)
+//               the line has been read); packed records (MODE 4): the stream position of the
+//               open line's first record
 // A record may only be staged while its line is the open one; otherwise the lane keeps it
 // pending (<= 4 per lane) and retries on its next tile.  LDS executes one wave's instructions
 // in order, so "written counts it" implies "the record is there", and "flushed moved on"
@@ -447,13 +463,16 @@ MQ_D void hot_apply(int op, int64_t* s, int64_t vb, bool is_null) {
 // so a clustered key range still fills every partition evenly — the run sizing counts on balanced partitions, which a hash
 // gives for free); a key off the lattice raises d_err[2] and is dropped: the caller gives the member up
 // (k_part_aggregate_idx).  The heavy-hitter table and the spill list stay on the real key.
+// MODE 4 (LATTICE, PACK): MODE 3 with the packed records above — a record carries e = idx / P in 16 bits, a line of
+// L / 8 segments holds 12 x L / 8 records, a run cap / 8 x 12; cnt[] counts records as before.
 template <typename FT, typename VT, int MODE = 0>
 __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
     const int8_t* const* __restrict__ cols, const int64_t* __restrict__ num_rows, int n_frags,
     int n_cols, RangeFilter flt, int kcol, int vcol, ScatterArgs g, Rec* __restrict__ scratch,
     uint32_t* __restrict__ cnt, SpillList sl) {
   constexpr bool DIRECT = MODE == 1;
-  constexpr bool LATTICE = MODE == 3;
+  constexpr bool LATTICE = MODE == 3 || MODE == 4;
+  constexpr bool PACK = MODE == 4;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   Rec* stage = (Rec*)smem_raw;                                      // [P][L] = kStageRecs records
   uint32_t* cursor = (uint32_t*)(smem_raw + kStageRecs * sizeof(Rec));  // [P]
@@ -478,6 +497,10 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
   const int wave = t >> 6, lane = t & 63;
   const int lgL = g.lgL;
   const uint32_t Lm1 = g.L - 1;
+  const int lgSpl = lgL - 3;  // log2(segments per line)
+  const int lgP = 31 - __builtin_clz((uint32_t)g.P);
+  const uint32_t run_recs = PACK ? (g.cap >> 3) * kPackRecs : g.cap;  // records a run holds
+  const uint32_t line_recs = PACK ? kPackRecs << lgSpl : g.L;         // records a staged line holds
   for (int i = t; i < 3 * g.P + 2; i += kPartBlock) cursor[i] = 0;
   for (int i = t; i < g.n_cand; i += kPartBlock) cand[i] = 0;
   if (t == 0) *sp_blk = 0;  // next == end: the first spill fetches a block
@@ -511,6 +534,21 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
     auto quad_of = [&]() -> int64_t { return (gt - base) * kSuperQuads + wave * 64 + lane; };
     // stage one record if its line is open; true = the record has left this lane
     auto try_stage = [&](int64_t key, int64_t vb, uint32_t p, uint32_t s) -> bool {
+      if (PACK) {
+        // segment q of the open line, position off - 12 q in it; the value with one 8-byte store, e with a 16-bit store of
+        // its own (never a read-modify-write of the word: another producer fills the other half at the same time)
+        const uint32_t off = s - lds_peek(&flushed[p]);  // (a line that is not open yet: beyond the line, unsigned)
+        if (off >= line_recs) return false;
+        asm volatile("" ::: "memory");
+        const uint32_t q = div12_small(off);
+        char* seg = (char*)(stage + ((size_t)p << lgL) + (q << 3));
+        const uint32_t u = off - q * kPackRecs;
+        ((int64_t*)seg)[u] = vb;
+        ((uint16_t*)(seg + kPackEntryOff))[u] = (uint16_t)key;
+        asm volatile("" ::: "memory");
+        atomicAdd(&written[p], 1u);
+        return true;
+      }
       if (lds_peek(&flushed[p]) != (s >> lgL)) return false;
       asm volatile("" ::: "memory");  // compiler order only: the LDS itself runs a wave in order
       stage[((size_t)p << lgL) + (s & Lm1)] = Rec{key, vb};
@@ -547,7 +585,7 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
       auto one_row = [&](int i, auto hot_aware) {
         bool park = false;
         uint32_t p = 0, s = 0;
-        int64_t vb = 0, rk = 0;  // rk: what the record carries — the key (DIRECT) or its kid
+        int64_t vb = 0, rk = 0;  // rk: what the record carries — the key (DIRECT), its kid, its lattice index or (PACK) entry
         if (i < cur.valid && filter_pass_narrow<FT>(flt, quad_get(cur.f, i)) &&
             (!DIRECT || (uint64_t)cur.k.v[i] - (uint64_t)g.kmin < (uint64_t)g.hm.d)) {
           const int64_t key = cur.k.v[i];
@@ -585,7 +623,7 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
             on_lattice = lattice_index(g, key, &idx);
             if (!on_lattice) atomicExch(sl.d_err + 2, 1);
             p = (uint32_t)idx & (uint32_t)(g.P - 1);
-            rk = (int64_t)idx;
+            rk = PACK ? (int64_t)(idx >> lgP) : (int64_t)idx;
           }
           if (!folded && on_lattice) {
             if (!LATTICE) {
@@ -595,7 +633,7 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
             // (the one key whose kid is the LDS tables' empty mark takes the spill list, like a record
             // that meets a full run)
             s = (MODE == 0 && rk == kEmptyKey64) ? g.cap : atomicAdd(&cursor[p], 1u);
-            if (s >= g.cap) spill_raw(sl, g, sp_blk, key, vb);
+            if (s >= run_recs) spill_raw(sl, g, sp_blk, key, vb);
             else park = !try_stage(rk, vb, p, s);
           }
         }
@@ -652,9 +690,8 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
   // Flusher lane `fid` owns segments fid + 256 k (k = 0..3); in pass k a wave covers 64
   // consecutive segments, so the segments of one line (<= 64) always share a pass and a wave.
   const int fid = (wave - kProdWaves) * 64 + lane;
-  const int lgSpl = lgL - 3;
-  uint32_t my_fl[kSegPerFlusher];
-  for (int k = 0; k < kSegPerFlusher; ++k) my_fl[k] = 0;
+  uint32_t my_fl[kSegPerFlusher], my_base[kSegPerFlusher];  // lines this lane has sent; PACK: their records
+  for (int k = 0; k < kSegPerFlusher; ++k) my_fl[k] = my_base[k] = 0;
   uint32_t idle = 0;
   for (;;) {
     const bool all_done = lds_peek(done) == (uint32_t)kProdWaves;  // read BEFORE the scan
@@ -665,14 +702,16 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
       const int p = seg >> lgSpl;
       const uint32_t sidx = (uint32_t)seg & ((1u << lgSpl) - 1);
       const uint32_t w = lds_peek(&written[p]);
-      const bool need = (w >> lgL) > my_fl[k] && (my_fl[k] << lgL) < g.cap;
+      const bool full = PACK ? w - my_base[k] >= line_recs : (w >> lgL) > my_fl[k];  // the open line is complete
+      const bool need = full && (my_fl[k] << lgL) < g.cap;
       asm volatile("" ::: "memory");
       flush_segments(need, ((uint32_t)p * g.B + b) * g.cap + (my_fl[k] << lgL) + sidx * kSegRecs, stage,
                      seg - lane, scratch);
       asm volatile("" ::: "memory");
       if (need) {
         my_fl[k] += 1;
-        if (sidx == 0) lds_poke(&flushed[p], my_fl[k]);  // after this wave's reads of the line
+        my_base[k] += line_recs;
+        if (sidx == 0) lds_poke(&flushed[p], PACK ? my_base[k] : my_fl[k]);  // after this wave's reads of the line
       }
       any_work |= need;
     }
@@ -694,13 +733,14 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
     const int p = seg >> lgSpl;
     const uint32_t sidx = (uint32_t)seg & ((1u << lgSpl) - 1);
     const uint32_t w = lds_peek(&written[p]);
-    const uint32_t rem = w - (my_fl[k] << lgL);  // < L
-    const bool need = sidx * kSegRecs < rem && (my_fl[k] << lgL) + sidx * kSegRecs < g.cap;
+    // records of the open line (fewer than a line holds); its segments hold 8 of them, or 12 packed
+    const uint32_t rem = w - (PACK ? my_base[k] : my_fl[k] << lgL);
+    const bool need = sidx * (PACK ? kPackRecs : (uint32_t)kSegRecs) < rem && (my_fl[k] << lgL) + sidx * kSegRecs < g.cap;
     flush_segments(need, ((uint32_t)p * g.B + b) * g.cap + (my_fl[k] << lgL) + sidx * kSegRecs, stage,
                    seg - lane, scratch);
     if (sidx == 0) {
       const uint32_t c = lds_peek(&cursor[p]);
-      cnt[(size_t)p * g.B + b] = c < g.cap ? c : g.cap;
+      cnt[(size_t)p * g.B + b] = c < run_recs ? c : run_recs;
     }
   }
   // the unused tail of this workgroup's last spill block must read as "no entry"
@@ -1284,7 +1324,8 @@ MQ_D int count_slot_of(const PartSlots& ps, int ns) {
 }
 
 // g: P, B, cap of the scatter; E = entries per unit (multiple of 4), slot_off / lds_table_bytes of the keyless table
-template <int MASK>
+// PACK: the runs hold the packed segments of k_part_scatter MODE 4 (twelve {value, 16-bit entry} per 128 bytes)
+template <int MASK, bool PACK = false>
 __global__ __launch_bounds__(kPartBlock) void k_part_aggregate_idx(PartGeom g, const Rec* __restrict__ scratch,
                                                                     const uint32_t* __restrict__ cnt, PartSlots ps,
                                                                     int64_t* __restrict__ acc) {
@@ -1307,9 +1348,47 @@ __global__ __launch_bounds__(kPartBlock) void k_part_aggregate_idx(PartGeom g, c
     const int wave = t >> 6, lane = t & 63;
     for (int b = wave; b < g.B; b += kPartBlock / 64) {
       uint32_t n = lcnt[b];
+      const Rec* run = scratch + ((size_t)p * g.B + b) * g.cap;
+      if (PACK) {
+        // a lane takes a pair of records: pair t lies in segment t / 6 at u = t % 6 — 16 bytes of values at 16 u, the two
+        // entries in the word at 96 + 4 u, nothing to exchange between lanes.  Three pairs per lane and the next three in flight: 60 bytes a lane, as
+        // many as the four 16-byte records of the unpacked walk, at the same register budget.
+        const uint32_t cap_p = (g.cap >> 3) * kPackRecs;
+        if (n > cap_p) n = cap_p;
+        if (!n) continue;
+        const uint32_t np = (n + 1) >> 1, lastp = np - 1;
+        struct Pair {
+          v2i64_t v;
+          uint32_t e;
+        };
+        auto load_pair = [&](uint32_t t) -> Pair {
+          if (t > lastp) t = lastp;  // clamped: always loadable
+          // t / 6: floor(t / 3) = mulhi(t, (2^33 + 1) / 3) >> 1 for every 32-bit t (the error t / (3 x 2^33) stays below 1/3)
+          const uint32_t sg = __umulhi(t, 0xaaaaaaabu) >> 2, u = t - sg * 6;
+          const char* seg = (const char*)run + (size_t)sg * 128;
+          Pair r;
+          r.v = *(const v2i64_t*)(seg + 16 * u);
+          r.e = *(const uint32_t*)(seg + kPackEntryOff + 4 * u);
+          return r;
+        };
+        auto one_pair = [&](const Pair& r, uint32_t t) {
+          const uint32_t e0 = r.e & 0xffffu, e1 = r.e >> 16;  // unsigned: a COUNT-only plan's entries pass 32 767
+          if (2 * t < n && e0 < g.E) apply_row<MASK>(smem_raw, g, ps, e0, (int64_t)r.v.x);
+          if (2 * t + 1 < n && e1 < g.E) apply_row<MASK>(smem_raw, g, ps, e1, (int64_t)r.v.y);  // (n odd: the last pair is half)
+        };
+        Pair c0 = load_pair(lane), c1 = load_pair(lane + 64), c2 = load_pair(lane + 128);
+        for (uint32_t base = 0; base < np; base += 192) {
+          const uint32_t i = base + lane, nx = i + 192;
+          const Pair n0 = load_pair(nx), n1 = load_pair(nx + 64), n2 = load_pair(nx + 128);
+          one_pair(c0, i);
+          one_pair(c1, i + 64);
+          one_pair(c2, i + 128);
+          c0 = n0; c1 = n1; c2 = n2;
+        }
+        continue;
+      }
       if (n > g.cap) n = g.cap;
       if (!n) continue;
-      const Rec* run = scratch + ((size_t)p * g.B + b) * g.cap;
       const uint32_t last = n - 1;
       auto at = [&](uint32_t i) -> uint32_t { return i < last ? i : last; };  // clamped: always loadable
       auto one = [&](const Rec& r, bool valid) {
@@ -2517,7 +2596,7 @@ hipError_t launch_scatter_v(const FastShape& fs, int grid, size_t lds, hipStream
   return launch_scatter_t<FT, double, MODE>(grid, lds, s, fv, c, fs.flt, kcol, vcol, g, b, sl);
 }
 
-// GROUP BY (MODE 0 hashed records, 3 lattice indices): the member for the filter column's type and the value column's
+// GROUP BY (MODE 0 hashed records, 3 lattice indices, 4 packed lattice entries): the member for the filter column's type and the value column's
 template <int MODE>
 hipError_t launch_scatter(const FastShape& fs, int grid, size_t lds, hipStream_t s, const FragView& fv, const Chunk& c,
                           int kcol, const ScatterArgs& g, const ScratchCarve& b, const SpillList& sl) {
@@ -2573,20 +2652,22 @@ LatticeArea lattice_area(const DevPlan& p, const PartPlanHost& h) {
 }
 
 using AggIdxKernel = decltype(&k_part_aggregate_idx<0>);
-AggIdxKernel aggregate_idx_member(int op_mask, size_t lds2) {
-  AggIdxKernel k = k_part_aggregate_idx<0>;
+template <bool PACK>
+AggIdxKernel aggregate_idx_member_t(int op_mask) {
   switch (op_mask) {
-    case 1 << SO_COUNT: k = k_part_aggregate_idx<(1 << SO_COUNT)>; break;
-    case (1 << SO_COUNT) | (1 << SO_SUM_F): k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_F))>; break;
-    case (1 << SO_COUNT) | (1 << SO_SUM_I): k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_I))>; break;
+    case 1 << SO_COUNT: return k_part_aggregate_idx<(1 << SO_COUNT), PACK>;
+    case (1 << SO_COUNT) | (1 << SO_SUM_F): return k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_F)), PACK>;
+    case (1 << SO_COUNT) | (1 << SO_SUM_I): return k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_I)), PACK>;
     case (1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN):
-      k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN))>;
-      break;
+      return k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_F) | (1 << SO_COUNT_NN)), PACK>;
     case (1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN):
-      k = k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN))>;
-      break;
-    default: break;
+      return k_part_aggregate_idx<((1 << SO_COUNT) | (1 << SO_SUM_I) | (1 << SO_COUNT_NN)), PACK>;
+    default: return k_part_aggregate_idx<0, PACK>;
   }
+}
+// pack: the runs hold packed segments (k_part_scatter MODE 4)
+AggIdxKernel aggregate_idx_member(int op_mask, size_t lds2, bool pack) {
+  const AggIdxKernel k = pack ? aggregate_idx_member_t<true>(op_mask) : aggregate_idx_member_t<false>(op_mask);
   (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
   return k;
 }
@@ -2703,7 +2784,10 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
       lg.lds_table_bytes = off;
     }
     const size_t lds2 = (size_t)lg.lds_table_bytes + (size_t)lg.B * 4;
-    const AggIdxKernel agg_idx = aggregate_idx_member(h.op_mask, lds2);
+    // packed records (a 16-bit entry): the default; every entry of a unit this member accepts fits, the comparison only
+    // says so where the LDS budget is read
+    const bool pack = !(opt_flags & MI355Q_OPT_NO_LATTICE_PACK) && per_unit <= 65535;
+    const AggIdxKernel agg_idx = aggregate_idx_member(h.op_mask, lds2, pack);
     ScatterArgs sl3 = sa;
     sl3.kmin = kmin;
     sl3.lat_stride = stride;
@@ -2711,6 +2795,8 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
     sl3.lat_card = card;
     if (trace) std::fprintf(stderr, "[mi355q] phase 2 member: k_part_aggregate_idx (stride %llu, %llu lattice points, %d units of %u entries)\n",
                             stride, (unsigned long long)card, lg.P, lg.E);
+    if (trace) std::fprintf(stderr, pack ? "[mi355q] lattice records: 12 per 128-byte segment (8-byte value, 16-bit entry)\n"
+                                         : "[mi355q] lattice records: 8 per 128-byte segment (16-byte {index, value})\n");
     // the table (the spill merges and the emission insert into it) and the accumulator
     RowInit ri{};
     ri.row_quad = p.row_quad;
@@ -2722,7 +2808,10 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
     (void)hipFuncSetAttribute((const void*)k_spill_merge, hipFuncAttributeMaxDynamicSharedMemorySize, h.g.ns_int * kSpillLds * 8);
     const SpillList sl0 = spills(b0);
     for (Chunk c = part_host::next_chunk(fv, 0, h.chunk_rows); c.nf > 0; c = part_host::next_chunk(fv, c.f0 + c.nf, h.chunk_rows)) {
-      e2 = timed.run([&] { return launch_scatter<3>(fs, h.g.B, h.lds1, s, fv, c, p.group_col, sl3, b0, sl0); });
+      e2 = timed.run([&] {
+        return pack ? launch_scatter<4>(fs, h.g.B, h.lds1, s, fv, c, p.group_col, sl3, b0, sl0)
+                    : launch_scatter<3>(fs, h.g.B, h.lds1, s, fv, c, p.group_col, sl3, b0, sl0);
+      });
       if (e2 != hipSuccess) return e2;
       hipLaunchKernelGGL(agg_idx, dim3(lg.P < h.grid2 ? lg.P : h.grid2), dim3(kPartBlock), lds2, s, lg, (const Rec*)b0.recs, b0.cnt,
                          h.ps, acc);

@@ -580,6 +580,10 @@ typedef struct mi355q_exec_options {
                                             have k_groupby_lds_prog evaluate the arguments' programs beside its LDS table
                                             (that kernel is no default: it lost to the two passes when measured; tests and
                                             tools/agg_prog_bench.py --group compare the two) */
+#define MI355Q_OPT_NO_LATTICE_PACK 16384u /* partitioned GROUP BY, lattice member: the 16-byte {index, value} records, eight
+                                            per 128-byte segment, instead of the packed ones (8-byte value, 16-bit entry
+                                            inside the unit, twelve per segment; tests and bench.py --opt-flags compare
+                                            the two) */
 
 /* per-call timing/selection report (what launchGpuCode logs,
  * QueryExecutionContext.cpp:334,364,579) */

@@ -211,6 +211,7 @@ OPT_NO_LATTICE_PART = 2048
 OPT_NO_AGG_PROGRAMS = 4096
 OPT_NO_GROUPED_AGG_PROGRAMS = 8192
 OPT_NO_LATTICE_PACK = 16384
+OPT_NO_JOIN_EXPAND = 32768   # grouped steps over a one-to-many join table stay in the row kernel (no k_join_expand)
 
 
 class ExecReport(C.Structure):

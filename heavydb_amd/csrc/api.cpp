@@ -892,6 +892,8 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
     return e;
   if (fast && !async && join && (e = try_route(out, [&] { return execute_join_gather(plan, in, o, q, d, n_cus, out, report, reserved); })) != kNotTaken)
     return e;
+  if (fast && !async && join && (e = try_route(out, [&] { return execute_join_expand(plan, in, o, q, d, n_cus, out, report, reserved); })) != kNotTaken)
+    return e;
   if (fast && !lds_direct && !async &&
       (e = try_route(out, [&] { return execute_perfect_twin(plan, in, o, q, n_cus, out, report, reserved); })) != kNotTaken)
     return e;

@@ -27,8 +27,8 @@ int64_t pass_budget(int64_t held_bytes) {
 
 // ------------------------------------------------------------------------------- the pass loop
 // The routes whose derived step reads TEMPORARY columns beside the stated ones (join gather: the inner side's columns and
-// the matched flag; affine twin: lattice indices; projection: the expressions' values; mask: the compiled filter's row
-// mask).  The columns of one PASS of fragments live in a DeviceCtx workspace sized from the free memory; per pass the
+// the matched flag; join expansion: the joined rows, stated columns included; affine twin: lattice indices; projection: the
+// expressions' values; mask: the compiled filter's row mask).  The columns of one PASS of fragments live in a DeviceCtx workspace sized from the free memory; per pass the
 // route's own pre-pass kernel fills them, the derived plan runs over the pass, and the passes' results are folded with
 // the reduce rule.  Workspace layout (every part 256-byte rounded):
 //   column chunks | pointer table | bytes_after_tab | row counts | 256 (64 error bytes) | bytes_after_err
@@ -57,6 +57,14 @@ struct PassLoop {
   bool inner_errors_not_taken = false;
   // affine twin: every pass's result must be the perfect-hash twin that was planned (else kNotTaken); null: no check
   const mi355q_qmd* twin = nullptr;
+  // join expansion only: the derived step runs over the JOINED rows.  derived_rows[f] = rows of the derived fragment that
+  // outer fragment f becomes: what cuts the passes, sizes the chunks and is the derived step's num_rows (a fragment nothing
+  // of which joins is left out of its pass's derived step); stated_tmp_width[c] != 0: stated column c is a temporary column
+  // of that storage width too (the pre-pass writes it), 0: the derived step does not read column c — its entry points at the
+  // fragment's first temporary chunk, which is valid, aligned and never read.  The pre-pass reads the caller's columns from
+  // a table of its own; d_tab is the derived step's table of ALL fragments of the pass, d_rows the OUTER row counts.
+  const int64_t* derived_rows = nullptr;
+  const int32_t* stated_tmp_width = nullptr;
 
   // ---- laid out by prepare()
   int nc2 = 0;
@@ -82,9 +90,14 @@ struct PassLoop {
     const int64_t budget = pass_budget(ws.bytes);
     int64_t row_bytes = 0;
     for (int k = 0; k < n_extra; ++k) row_bytes += width[k];
+    int n_tmp = n_extra;
+    for (int c = 0; stated_tmp_width && c < nc; ++c) {
+      row_bytes += stated_tmp_width[c];
+      n_tmp += stated_tmp_width[c] != 0;
+    }
     // every (fragment, column) chunk starts on a 16-byte boundary: the fast families want aligned columns
     // (worst case: every fragment of a pass pads every chunk once)
-    const int64_t pad = mask_column ? 32 : 16 * (int64_t)n_extra;
+    const int64_t pad = mask_column ? 32 : 16 * (int64_t)n_tmp;
     pass_rows = std::max<int64_t>(budget / std::max<int64_t>(row_bytes, 1), max_frag_rows);
     if (o.pass_rows > 0) pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);  // tests: several passes
     if (pass_rows > total_rows) pass_rows = total_rows;
@@ -116,20 +129,32 @@ struct PassLoop {
     hipStream_t s = rs.s;
     if (clear_err_word) HIP_TRY(hipMemsetAsync(d_err, 0, 64, s));
     HIP_TRY(hipMemcpyAsync(d_rows, in->num_rows, sizeof(int64_t) * (size_t)nf, hipMemcpyHostToDevice, s));
-    if (int32_t e = rs.begin_timing(report)) return e;
+    if (!rs.ev0)  // (the join expansion has begun the span already: its count and scan run ahead of the passes)
+      if (int32_t e = rs.begin_timing(report)) return e;
     cols2.resize((size_t)nf * nc2);
+    const int64_t* frag_rows = derived_rows ? derived_rows : in->num_rows;
+    std::vector<int64_t> rows2;  // join expansion: the row counts of the derived fragments a pass runs over
     int pass = 0, f = 0;
     while (f < nf) {
       // a pass holds at least one fragment; the next one joins while the pass stays within pass_rows
       int f1 = f;
       int64_t rows = 0, off = 0;
-      while (f1 < nf && (f1 == f || rows + in->num_rows[f1] <= pass_rows)) {
-        for (int c = 0; c < nc; ++c) cols2[(size_t)(f1 - f) * nc2 + c] = in->col_buffers[(size_t)f1 * nc + c];
+      while (f1 < nf && (f1 == f || rows + frag_rows[f1] <= pass_rows)) {
+        const char* first_tmp = base + off;
+        for (int c = 0; c < nc; ++c) {
+          const void*& col = cols2[(size_t)(f1 - f) * nc2 + c];
+          if (stated_tmp_width && stated_tmp_width[c]) {
+            col = base + off;
+            off += (frag_rows[f1] * stated_tmp_width[c] + 15) & ~15ll;
+          } else {
+            col = derived_rows ? (const void*)first_tmp : in->col_buffers[(size_t)f1 * nc + c];
+          }
+        }
         for (int k = 0; k < n_extra; ++k) {
           cols2[(size_t)(f1 - f) * nc2 + nc + k] = base + off;
-          off += mask_column ? filter_mask_chunk_bytes(in->num_rows[f1]) : (in->num_rows[f1] * width[k] + 15) & ~15ll;
+          off += mask_column ? filter_mask_chunk_bytes(frag_rows[f1]) : (frag_rows[f1] * width[k] + 15) & ~15ll;
         }
-        rows += in->num_rows[f1];
+        rows += frag_rows[f1];
         ++f1;
       }
       if (off > col_region) return MI355Q_ERR_OUT_OF_GPU_MEM;  // (cannot happen: the region is sized for it)
@@ -143,6 +168,20 @@ struct PassLoop {
       in2.n_frags = pnf;
       in2.col_buffers = cols2.data();
       in2.num_rows = in->num_rows + f;
+      if (derived_rows) {  // the pass's derived fragments: the ones that have rows (the pre-pass has synchronised: cols2 is ours again)
+        rows2.clear();
+        for (int i = 0; i < pnf; ++i) {
+          if (derived_rows[f + i] <= 0) continue;
+          if ((size_t)i != rows2.size()) std::copy_n(&cols2[(size_t)i * nc2], nc2, &cols2[rows2.size() * nc2]);
+          rows2.push_back(derived_rows[f + i]);
+        }
+        in2.n_frags = (int32_t)rows2.size();
+        in2.num_rows = rows2.data();
+        if (rows2.empty()) {  // (cannot happen while something joins: rowless fragments ride with their neighbours)
+          f = f1;
+          continue;
+        }
+      }
       mi355q_exec_options o2 = o;
       o2.stream = s;
       o2.out_buffer = pass == 0 && first_into_out_buffer ? o.out_buffer : nullptr;
@@ -594,7 +633,7 @@ int32_t execute_multi_value(const mi355q_plan* plan, const mi355q_inputs* in, co
 // "matched" column the derived step filters on.  The derived plan has no join, the same targets over those columns and the
 // SAME layout (asserted: the descriptor of the derived plan must equal the stated one bit for bit), so its result is the
 // step's result and every grouped family applies (LDS members, the partitioned families).  One-to-many tables change the
-// row multiplicity and stay in the row kernel.  kNotTaken when the shape does not call for it.
+// row multiplicity: execute_join_expand below.  kNotTaken when the shape does not call for it.
 int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
                             const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
   if (plan->join_outer_col < 0 || plan->n_group_cols < 1 || plan->n_exprs != 0 || o.kernel_variant == 1 || o.force_generic ||
@@ -687,6 +726,192 @@ int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, co
       }))
     return e;
   if (int32_t e = rs.finish(report, pl.acc, 0, *plan, *in, total_rows)) return e;
+  *out = pl.res.release();
+  return MI355Q_OK;
+}
+
+// The same steps over a ONE-TO-MANY join table ("real fact JOIN dim workloads have duplicates").  The reference's join
+// loop encloses the row function's body, so the step over fact JOIN dim IS the stated step, without the join, over the joined
+// rows: k_join_expand_count / _scan count them per tile and fragment, k_join_expand_write lays them down as dense temporary
+// columns — the outer columns the derived plan reads copied as stored (every encoding survives: the derived plan keeps the
+// descriptors), the inner columns gathered through the payload, NULL for an unmatched LEFT row — and outer fragment f becomes
+// one derived fragment of rows2[f] rows, in (outer row, payload) order.  The quals stay in the derived plan: they read outer
+// columns only and hold per joined row (rows they drop are expanded and dropped by the derived step; constrained_not_null
+// is part of the layout anyway); an INNER join needs no "matched" column, its unmatched rows have no joined row.  The derived
+// plan has the SAME layout (asserted bit for bit), so every grouped family applies.  kNotTaken when the shape does not call
+// for it.
+int32_t execute_join_expand(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                            const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  if (plan->join_outer_col < 0 || plan->n_group_cols < 1 || plan->n_exprs != 0 || o.kernel_variant == 1 || o.force_generic ||
+      (o.flags & MI355Q_OPT_NO_JOIN_EXPAND) || (d.join_hash_type != 2 && d.join_hash_type != 3) ||
+      q.desc_type == MI355Q_NON_GROUPED_AGGREGATE)
+    return kNotTaken;
+  const int nc = plan->n_cols, nf = in->n_frags;
+  const bool left = plan->join_kind == MI355Q_JOIN_LEFT;
+  int64_t total_rows = 0, max_frag_rows = 0;
+  if (frag_row_totals(*in, &total_rows, &max_frag_rows)) return kNotTaken;  // (a negative count: the plain step's to refuse)
+  // Both thresholds are the gather route's ROUTING CONSTANTS, not crossovers measured for this route: the input size from
+  // which the large-input families are planned at all, and the perfect-hash table the row kernel aggregates in a
+  // per-workgroup LDS copy (launch_generic).  (kernel_variant 2 = "the large-input members": how the tests reach this route
+  // with small tables)
+  if (nf < 1 || (o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
+  if (o.kernel_variant != 2 && q.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && q.entry_count * (int64_t)q.row_size <= 64 * 1024)
+    return kNotTaken;
+  // the inner columns the targets read, in order of first use: plain columns, appended behind the stated ones
+  JoinExpand je{};
+  int32_t width[MI355Q_MAX_COLS];
+  mi355q_plan p2 = *plan;
+  for (int t = 0; t < plan->n_targets; ++t) {
+    const mi355q_target& tg = plan->targets[t];
+    if (tg.agg == MI355Q_PROJECT_KEY || tg.table == 0 || tg.col < 0) continue;
+    if (tg.col >= plan->n_inner_cols) return kNotTaken;
+    int j = 0;
+    while (j < je.n_inner && je.inner_col[j] != tg.col) ++j;
+    if (j == je.n_inner) {
+      const mi355q_col_desc& cd = plan->inner_cols[tg.col];
+      if (cd.encoding != MI355Q_ENC_NONE || (cd.logical_type != 0 && cd.logical_type != cd.type)) return kNotTaken;
+      if (nc + je.n_inner + 1 > MI355Q_MAX_COLS) return kNotTaken;
+      je.inner_col[j] = tg.col;
+      je.inner_dst[j] = nc + j;
+      je.inner_w[j] = width[j] = plain_width(cd.type);
+      je.null_pat[j] = cd.type == MI355Q_DOUBLE ? kNullDoubleBits
+                       : cd.type == MI355Q_FLOAT ? (int64_t)(uint32_t)kNullFloatBits : plain_int_null(cd.type);
+      p2.cols[nc + j] = cd;
+      // (nullable under an outer join, resolve_targets' rule; the RANGE stays the column's own, as the layout decisions read it)
+      if (left) p2.cols[nc + j].nullable = 1;
+      p2.col_ranges[nc + j] = plan->inner_col_ranges[tg.col];
+      ++je.n_inner;
+    }
+    p2.targets[t].table = 0;
+    p2.targets[t].col = nc + j;
+  }
+  const int nc2 = nc + je.n_inner;
+  p2.n_cols = nc2;
+  p2.join_outer_col = -1;
+  p2.join_table = nullptr;
+  p2.n_join_cols = 0;
+  p2.join_kind = MI355Q_JOIN_INNER;
+  p2.n_inner_cols = 0;
+  mi355q_qmd q2;
+  if (qmd_init(p2, &q2) != MI355Q_OK || std::memcmp(&q, &q2, sizeof(q)) != 0) return kNotTaken;  // the same layout, or not this way
+  if (reserved) {
+    // nothing is launched, so no count exists: the derived step over the OUTER fragments' shape (the pointers are not looked at)
+    route_note("k_join_expand (joined rows as dense columns)");
+    std::vector<const void*> fake((size_t)nf * nc2, nullptr);
+    mi355q_inputs in2 = *in;
+    in2.col_buffers = fake.data();
+    in2.inner_col_buffers = nullptr;
+    return execute_impl(&p2, &in2, &o, out, report, nullptr, reserved);
+  }
+  // the stated columns the derived plan reads: expanded as stored.  The others (the join key, usually) are not.
+  int32_t tmp_width[MI355Q_MAX_COLS] = {};
+  {
+    bool read[MI355Q_MAX_COLS] = {};
+    const auto reads = [&](int c) { if (c >= 0 && c < nc) read[c] = true; };
+    for (int g = 0; g < plan->n_group_cols; ++g) reads(plan->group_cols[g]);
+    for (int t = 0; t < plan->n_targets; ++t) {
+      const mi355q_target& tg = p2.targets[t];
+      if (tg.agg != MI355Q_PROJECT_KEY && tg.table == 0) reads(tg.col);
+      if (tg.agg == MI355Q_COUNT_IF || tg.agg == MI355Q_SUM_IF) reads(tg.cond.col);
+    }
+    for (int k = 0; k < plan->n_quals; ++k) reads(plan->quals[k].col);
+    for (int c = 0; c < nc; ++c) {
+      if (!read[c]) continue;
+      const int code = col_type_code(plan->cols[c]);
+      if (code < 0) return kNotTaken;
+      je.outer_col[je.n_outer] = c;
+      je.outer_w[je.n_outer++] = tmp_width[c] = type_width(code);
+    }
+  }
+  RouteScope rs(in->device_id, o.stream);
+  if (rs.status) return rs.status;
+  hipStream_t s = rs.s;
+  // ---- count and scan, once over all fragments: the tiles' and the fragments' joined rows
+  const int64_t tile_rows = projection_tile_rows();
+  std::vector<int64_t> h_meta((size_t)2 * nf + 1);  // tile_start [nf + 1] | num_rows [nf]
+  bool key_aligned = true;
+  for (int f = 0; f < nf; ++f) {
+    h_meta[f + 1] = h_meta[f] + (in->num_rows[f] + tile_rows - 1) / tile_rows;
+    h_meta[(size_t)nf + 1 + f] = in->num_rows[f];
+    key_aligned = key_aligned && ((uintptr_t)in->col_buffers[(size_t)f * nc + d.join_cols[0]] & 15) == 0;
+  }
+  const int64_t n_tiles = h_meta[nf];
+  const int64_t meta_bytes = (((int64_t)h_meta.size() * 8) + 255) & ~255ll, tab_bytes = ((int64_t)sizeof(void*) * nf * nc + 255) & ~255ll;
+  const int64_t tiles_bytes = (n_tiles * 8 + 255) & ~255ll, frags_bytes = ((int64_t)nf * 8 + 255) & ~255ll;
+  DevWord area;  // tile_start | num_rows | the stated columns' table | tile_cnt | tile_base | frag_first | frag_rows
+  if (hipMalloc(&area.p, (size_t)(meta_bytes + tab_bytes + 2 * tiles_bytes + 2 * frags_bytes)) != hipSuccess) {
+    (void)hipGetLastError();
+    return kNotTaken;
+  }
+  char* ap = (char*)area.p;
+  je.tile_start = (const int64_t*)ap;
+  je.num_rows = je.tile_start + nf + 1;
+  je.src = (const int8_t* const*)(ap + meta_bytes);
+  je.tile_cnt = (unsigned long long*)(ap + meta_bytes + tab_bytes);
+  je.tile_base = (unsigned long long*)(ap + meta_bytes + tab_bytes + tiles_bytes);
+  je.frag_first = (unsigned long long*)(ap + meta_bytes + tab_bytes + 2 * tiles_bytes);
+  je.frag_rows = (unsigned long long*)(ap + meta_bytes + tab_bytes + 2 * tiles_bytes + frags_bytes);
+  je.n_frags = nf;
+  je.nc = nc;
+  je.nc2 = nc2;
+  je.n_tiles = n_tiles;
+  je.left = left;
+  je.quad_key = d.join_n_keys == 1 && key_aligned && (d.join_types[0] == MI355Q_INT32 || d.join_types[0] == MI355Q_INT64)
+                    ? type_width(d.join_types[0]) : 0;
+  HIP_TRY(hipMemcpyAsync(ap, h_meta.data(), h_meta.size() * 8, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ap + meta_bytes, in->col_buffers, sizeof(void*) * (size_t)nf * nc, hipMemcpyHostToDevice, s));
+  if (int32_t e = rs.begin_timing(report)) return e;
+  HIP_TRY(launch_join_expand_count(d, je, n_cus, s));
+  std::vector<int64_t> rows2((size_t)nf);
+  HIP_TRY(hipMemcpyAsync(rows2.data(), je.frag_rows, sizeof(int64_t) * (size_t)nf, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the one synchronisation the sizes cost
+  int64_t total2 = 0, max_rows2 = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (rows2[f] < 0 || rows2[f] >= ((int64_t)1 << 31)) return kNotTaken;
+    total2 += rows2[f];
+    max_rows2 = std::max(max_rows2, rows2[f]);
+  }
+  mi355q_inputs in_outer = *in;  // the derived step has no inner side
+  in_outer.inner_col_buffers = nullptr;
+  if (total2 == 0) {
+    // nothing joins at all: the derived step once over one fragment without rows, for the stated, initialised layout
+    // (a family that refuses such a step gives the route up)
+    if (rs.ctx.gather.grow(256) != hipSuccess) {
+      (void)hipGetLastError();
+      return kNotTaken;
+    }
+    std::vector<const void*> cols0((size_t)nc2, rs.ctx.gather.p);
+    const int64_t no_rows = 0;
+    in_outer.n_frags = 1;
+    in_outer.col_buffers = cols0.data();
+    in_outer.num_rows = &no_rows;
+    mi355q_exec_options o2 = o;
+    o2.stream = s;
+    mi355q_result* r2 = nullptr;
+    mi355q_exec_report acc{};
+    if (mi355q_execute(&p2, &in_outer, &o2, &r2, &acc)) return kNotTaken;
+    ResultPtr res(r2);
+    if (int32_t e = rs.finish(report, acc, 2, *plan, *in, total_rows)) return e;
+    *out = res.release();
+    return MI355Q_OK;
+  }
+  PassLoop pl(rs.ctx.gather, nc, je.n_inner, width, &p2);
+  pl.clear_err_word = false;
+  pl.derived_rows = rows2.data();
+  pl.stated_tmp_width = tmp_width;
+  if (int32_t e = pl.prepare(&in_outer, o, total2, max_rows2)) return e;
+  if (int32_t e = pl.run(rs, &in_outer, o, report, [&](int f, int pnf) -> int32_t {
+        je.frag0 = f;
+        je.n_pass_frags = pnf;
+        je.pass_tile0 = h_meta[f];
+        je.pass_tiles = h_meta[f + pnf] - h_meta[f];
+        je.dst = (int8_t* const*)pl.d_tab;
+        HIP_TRY(launch_join_expand_write(d, je, n_cus, s));
+        HIP_TRY(hipStreamSynchronize(s));  // (cols2 is re-used by the next pass; the step below synchronises anyway)
+        return MI355Q_OK;
+      }))
+    return e;
+  if (int32_t e = rs.finish(report, pl.acc, 2, *plan, *in, total_rows)) return e;  // (+ 2: count and scan)
   *out = pl.res.release();
   return MI355Q_OK;
 }
@@ -1508,6 +1733,15 @@ int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const B
                        const mi355q_exec_options& o, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
   const int nc = rest.n_cols, nc2 = nc + 1, nf = in->n_frags;
   if (nc2 > MI355Q_MAX_COLS || rest.n_quals != 0 || rest.n_exprs != 0) return kNotTaken;
+  // `arg IS NOT NULL` on an aggregate's own argument is part of the LAYOUT (constrained_not_null, plan.cpp resolve_targets: the
+  // slot's initial value and its NULL handling), and the masked plan states no quals: its table would not be the stated one
+  for (int k = 0; k < plan->n_quals && k < MI355Q_MAX_QUALS; ++k) {
+    if (MI355Q_QUAL_OP(plan->quals[k].op) != MI355Q_IS_NOT_NULL) continue;
+    for (int t = 0; t < plan->n_targets && t < MI355Q_MAX_TARGETS; ++t) {
+      const mi355q_target& tg = plan->targets[t];
+      if (tg.agg != MI355Q_PROJECT_KEY && tg.agg != MI355Q_PROJECT && tg.table == 0 && tg.col == plan->quals[k].col) return kNotTaken;
+    }
+  }
   mi355q_plan mp = rest;
   mp.n_cols = nc2;
   std::memset(&mp.cols[nc], 0, sizeof(mp.cols[nc]));

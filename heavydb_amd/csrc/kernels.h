@@ -374,6 +374,35 @@ hipError_t launch_projection(const DevPlan& p, const ProjSpec& ps, const DevExpr
 hipError_t launch_projection_count_live(const int64_t* keys, int64_t stride_quads, int64_t entries, unsigned long long* d_count,
                                         hipStream_t s);
 
+// grouped joins over a ONE-TO-MANY table: the joined rows as dense columns (kernels_proj.hip k_join_expand_count / _scan /
+// _write, api_routes.cpp execute_join_expand).  Tiles are the Projection's (projection_tile_rows() outer rows of one fragment);
+// every pointer is device memory.  `p` carries the join table, the key columns and the inner columns.
+struct JoinExpand {
+  // ---- all fragments: what count and scan read and write
+  const int8_t* const* src;        // [frag][nc] the stated columns
+  const int64_t* num_rows;         // [frag] outer rows
+  const int64_t* tile_start;       // [frag + 1] first tile of each fragment
+  int32_t n_frags, nc;
+  int64_t n_tiles;
+  unsigned long long* tile_cnt;    // [tile] joined rows of the tile (count)
+  unsigned long long* tile_base;   // [tile] joined rows of the tiles before it in its fragment (scan)
+  unsigned long long* frag_first;  // [frag] joined rows of the fragments before it (scan's intermediate)
+  unsigned long long* frag_rows;   // [frag] joined rows of the fragment: the derived fragment's row count (scan)
+  int32_t left;                    // LEFT join: an unmatched row is one joined row, the inner columns NULL
+  int32_t quad_key;                // 4 / 8: ONE plain INT32 / INT64 key column in 16-byte aligned chunks, read as quads; 0: decode_int
+  // ---- one pass: fragments [frag0, frag0 + n_pass_frags), what write reads
+  int32_t frag0, n_pass_frags;
+  int64_t pass_tile0, pass_tiles;  // = tile_start[frag0], tile_start[frag0 + n_pass_frags] - tile_start[frag0]
+  int8_t* const* dst;              // [pass fragment][nc2] the derived step's column table
+  int32_t nc2;
+  int32_t n_outer, n_inner;
+  int32_t outer_col[MI355Q_MAX_COLS], outer_w[MI355Q_MAX_COLS];  // stated columns copied as stored, and their storage widths
+  int32_t inner_col[MI355Q_MAX_COLS], inner_dst[MI355Q_MAX_COLS], inner_w[MI355Q_MAX_COLS];  // inner column -> derived column
+  int64_t null_pat[MI355Q_MAX_COLS];  // what an unmatched LEFT row gets (k_join_gather's patterns)
+};
+hipError_t launch_join_expand_count(const DevPlan& p, const JoinExpand& je, int n_cus, hipStream_t s);  // count, then scan
+hipError_t launch_join_expand_write(const DevPlan& p, const JoinExpand& je, int n_cus, hipStream_t s);
+
 // the row mask of a compiled filter with program atoms (kernels_filter.hip): one byte per row, 1 = the row passes
 int64_t filter_mask_chunk_bytes(int64_t n_rows);  // bytes of one fragment's mask chunk (16-byte multiple)
 bool filter_mask_eligible(const BoolFilter& bf, const FragView& fv);

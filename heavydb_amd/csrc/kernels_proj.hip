@@ -1407,6 +1407,278 @@ __global__ __launch_bounds__(kBlock) void k_proj_count_live(const int64_t* keys,
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 
+// ---- GROUPED steps over a ONE-TO-MANY join: the joined rows as dense temporary columns (api_routes.cpp execute_join_expand).
+// The join loop encloses the row function's body (IRCodegen.cpp:1233 codegenJoinLoops), so a grouped step over fact JOIN dim is
+// the same step WITHOUT the join over the joined rows — which every grouped family takes.  Three kernels over the Projection's
+// tiles, none of which waits for another workgroup (the host has to know the joined row count before it can size the columns,
+// so there is nothing a look-back could save):
+//   k_join_expand_count   joined rows per tile: the probe over the key column(s) alone, one plain 8-byte store per tile;
+//   k_join_expand_scan    one workgroup: a tile's first joined row inside its fragment, the fragments' joined row counts;
+//   k_join_expand_write   probes again and lays the joined rows of a pass of fragments down: (outer row, payload) order,
+//                         lane t of a step writes entry e0 + t of every column, whichever row the entry belongs to.
+static_assert(sizeof(JoinExpand) + sizeof(DevPlan) <= 3968, "the expansion kernels take their arguments by value: the kernel argument segment holds 4 KB");
+// the fragment a tile belongs to: tile_start[f] <= tile < tile_start[f + 1] (fragments without rows own no tile)
+MQ_D int expand_tile_frag(const JoinExpand& a, int64_t tile) {
+  int lo = 0, hi = a.n_frags;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.tile_start[mid] <= tile) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+// join_lookup (rowfunc.h) for the ONE-TO-MANY tables — [offsets | counts | payload] (perfect) / [keys | offsets | counts |
+// payload] (keyed) — with the key's components in registers: every loop over the components has a fixed trip count, so no
+// array is indexed at run time (join_lookup's key and its packed words live in scratch memory).  The hash is murmur1_words
+// over pack_join_key's words, the probe keyed_slot_of's.
+MQ_D JoinMatch expand_lookup(const DevPlan& p, const int64_t (&k)[MI355Q_MAX_GROUP_COLS]) {
+  JoinMatch m{nullptr, -1, 0};
+  const int64_t n = p.join_entries;
+  int64_t slot = -1;
+  const int32_t* offsets;
+  if (p.join_hash_type == 2) {
+    offsets = (const int32_t*)p.join_buf;
+    if (k[0] >= p.join_min && k[0] <= p.join_max) slot = k[0] - p.join_min;
+  } else {
+    const int nk = p.join_n_keys, w = p.join_width;
+    const uint32_t entries = (uint32_t)n;
+    offsets = (const int32_t*)((const int8_t*)p.join_buf + (size_t)n * nk * w);
+    if (entries) {
+      const uint32_t mm = 0xc6a4a793u;
+      uint32_t h = (uint32_t)((w == 4 ? nk : 2 * nk) * 4) * mm;
+#pragma unroll
+      for (int i = 0; i < MI355Q_MAX_GROUP_COLS; ++i) {
+        if (i >= nk) continue;
+        h += (uint32_t)(uint64_t)k[i];
+        h *= mm;
+        h ^= h >> 16;
+        if (w != 4) {
+          h += (uint32_t)((uint64_t)k[i] >> 32);
+          h *= mm;
+          h ^= h >> 16;
+        }
+      }
+      h *= mm;
+      h ^= h >> 10;
+      h *= mm;
+      h ^= h >> 17;
+      h %= entries;
+      uint32_t hp = h;
+      do {
+        bool same = true, empty;
+        if (w == 4) {
+          const int32_t* e = (const int32_t*)p.join_buf + (size_t)hp * nk;
+#pragma unroll
+          for (int i = 0; i < MI355Q_MAX_GROUP_COLS; ++i)
+            if (i < nk) same = same && e[i] == (int32_t)k[i];
+          empty = e[0] == kEmptyKey32;
+        } else {
+          const int64_t* e = (const int64_t*)p.join_buf + (size_t)hp * nk;
+#pragma unroll
+          for (int i = 0; i < MI355Q_MAX_GROUP_COLS; ++i)
+            if (i < nk) same = same && e[i] == k[i];
+          empty = e[0] == kEmptyKey64;
+        }
+        if (same) slot = hp;
+        if (same || empty) break;
+        hp = hp + 1 == entries ? 0 : hp + 1;
+      } while (hp != h);
+    }
+  }
+  if (slot >= 0) {
+    const int32_t off = offsets[slot];
+    if (off >= 0) {
+      m.count = offsets[n + slot];
+      m.ids = offsets + 2 * n + off;
+    }
+  }
+  return m;
+}
+// the matching set of outer row `pos` (a NULL key component matches nothing)
+MQ_D JoinMatch expand_row_matches(const DevPlan& p, const int8_t* const* fc, int64_t pos) {
+  int64_t k[MI355Q_MAX_GROUP_COLS] = {0, 0, 0, 0};
+  bool null_key = false;
+#pragma unroll
+  for (int i = 0; i < MI355Q_MAX_GROUP_COLS; ++i) {
+    if (i >= p.join_n_keys) continue;
+    k[i] = decode_int(fc[p.join_cols[i]], p.join_types[i], pos);
+    null_key = null_key || (p.join_nullables[i] && k[i] == int_null_of(p.join_types[i]));
+  }
+  if (null_key) return JoinMatch{nullptr, -1, 0};
+  return expand_lookup(p, k);
+}
+// the matching sets of the four rows r .. r + 3 of a lane's quad; rows behind the fragment's end (n) match nothing
+MQ_D void expand_quad_matches(const DevPlan& p, const JoinExpand& a, const int8_t* const* fc, int64_t r, int64_t n, JoinMatch (&jm)[4]) {
+  if (a.quad_key && r + 4 <= n) {  // ONE plain INT32 / INT64 key: the quad's four keys in one (two) 16-byte loads
+    RawQuad q;
+    load_raw_quad(fc[p.join_cols[0]], a.quad_key, r >> 2, q);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t k[MI355Q_MAX_GROUP_COLS] = {raw_elem(q, a.quad_key, i), 0, 0, 0};
+      jm[i] = p.join_nullables[0] && k[0] == int_null_of(p.join_types[0]) ? JoinMatch{nullptr, -1, 0} : expand_lookup(p, k);
+    }
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) jm[i] = r + i < n ? expand_row_matches(p, fc, r + i) : JoinMatch{nullptr, -1, 0};
+}
+MQ_D unsigned long long expand_rows_of(const JoinMatch& jm, bool inside, bool left) {
+  return jm.count > 0 ? (unsigned long long)jm.count : (left && inside) ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(kBlock) void k_join_expand_count(DevPlan p, JoinExpand a) {
+  __shared__ unsigned long long s_w[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool left = a.left != 0;
+  for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
+    const int f = expand_tile_frag(a, tile);
+    const int8_t* const* fc = a.src + (size_t)f * a.nc;
+    const int64_t n = a.num_rows[f];
+    const int64_t row0 = (tile - a.tile_start[f]) * kTileRows;
+    unsigned long long c = 0;
+#pragma unroll 1
+    for (int u = 0; u < kIters; ++u) {
+      const int64_t r = row0 + (int64_t)u * kIterRows + tid * 4;
+      if (r >= n) break;
+      JoinMatch jm[4];
+      expand_quad_matches(p, a, fc, r, n, jm);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c += expand_rows_of(jm[i], r + i < n, left);
+    }
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if (lane == 0) s_w[wave] = c;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long t = 0;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) t += s_w[w];
+      a.tile_cnt[tile] = t;
+    }
+    __syncthreads();
+  }
+}
+
+// ONE workgroup of 1 024 lanes, a run of tiles each (the shape of k_proj_scan_tiles): the prefix over all tiles, the fragments'
+// first joined rows and totals from it, then every tile's prefix made relative to its fragment
+__global__ __launch_bounds__(1024) void k_join_expand_scan(JoinExpand a) {
+  __shared__ unsigned long long s_sum[1024];
+  const int tid = threadIdx.x;
+  const int64_t per = (a.n_tiles + 1023) / 1024;
+  const int64_t lo = (int64_t)tid * per < a.n_tiles ? (int64_t)tid * per : a.n_tiles, hi = lo + per < a.n_tiles ? lo + per : a.n_tiles;
+  unsigned long long sum = 0;
+  for (int64_t i = lo; i < hi; ++i) sum += a.tile_cnt[i];
+  s_sum[tid] = sum;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const unsigned long long o = tid >= d ? s_sum[tid - d] : 0ull;
+    __syncthreads();
+    s_sum[tid] += o;
+    __syncthreads();
+  }
+  const unsigned long long total = s_sum[1023];
+  unsigned long long run = s_sum[tid] - sum;
+  for (int64_t i = lo; i < hi; ++i) {
+    a.tile_base[i] = run;
+    run += a.tile_cnt[i];
+  }
+  __syncthreads();  // (the prefixes other lanes of this workgroup wrote are read below)
+  for (int f = tid; f < a.n_frags; f += 1024) {
+    const int64_t t0 = a.tile_start[f], t1 = a.tile_start[f + 1];
+    const unsigned long long b0 = t0 < a.n_tiles ? a.tile_base[t0] : total, b1 = t1 < a.n_tiles ? a.tile_base[t1] : total;
+    a.frag_first[f] = b0;
+    a.frag_rows[f] = b1 - b0;
+  }
+  __syncthreads();
+  for (int64_t i = lo; i < hi; ++i) a.tile_base[i] -= a.frag_first[expand_tile_frag(a, i)];
+}
+
+__global__ __launch_bounds__(kBlock) void k_join_expand_write(DevPlan p, JoinExpand a) {
+  // one sub-tile (kIterRows outer rows): the exclusive prefix of the rows' joined-row counts and the rows' payload runs
+  __shared__ unsigned long long s_pre[kIterRows];
+  __shared__ const int32_t* s_ids[kIterRows];
+  __shared__ unsigned long long s_w[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool left = a.left != 0;
+  for (int64_t tile = a.pass_tile0 + blockIdx.x; tile < a.pass_tile0 + a.pass_tiles; tile += gridDim.x) {
+    if (a.tile_cnt[tile] == 0) continue;  // (uniform: nothing of this tile joins)
+    const int f = expand_tile_frag(a, tile);
+    const int8_t* const* fc = a.src + (size_t)f * a.nc;
+    int8_t* const* dc = a.dst + (size_t)(f - a.frag0) * a.nc2;
+    const int64_t n = a.num_rows[f];
+    const int64_t row0 = (tile - a.tile_start[f]) * kTileRows;
+    int64_t sub_base = (int64_t)a.tile_base[tile];  // first joined row of the sub-tile in the derived fragment
+#pragma unroll 1
+    for (int u = 0; u < kIters; ++u) {
+      const int64_t sub0 = row0 + (int64_t)u * kIterRows;
+      if (sub0 >= n) break;  // (uniform)
+      const int64_t r = sub0 + tid * 4;
+      JoinMatch jm[4];
+      expand_quad_matches(p, a, fc, r, n, jm);
+      unsigned long long cnt[4], c = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        cnt[i] = expand_rows_of(jm[i], r + i < n, left);
+        c += cnt[i];
+      }
+      unsigned long long inc = c;
+      for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long o = __shfl(inc, lane - d < 0 ? lane : lane - d, 64);
+        if (lane >= d) inc += o;
+      }
+      if (lane == 63) s_w[wave] = inc;
+      __syncthreads();
+      unsigned long long before = inc - c, sub_total = 0;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) {
+        const unsigned long long t = s_w[w];
+        if (w < wave) before += t;
+        sub_total += t;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        s_pre[tid * 4 + i] = before;
+        s_ids[tid * 4 + i] = jm[i].count > 0 ? jm[i].ids : nullptr;
+        before += cnt[i];
+      }
+      __syncthreads();
+      // entry e of the sub-tile belongs to the LAST row whose prefix is <= e (rows without joined rows share their successor's)
+      for (unsigned long long e = tid; e < sub_total; e += kBlock) {
+        int lo = 0, hi = kIterRows;
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (s_pre[mid] <= e) lo = mid;
+          else hi = mid;
+        }
+        const int32_t* ids = s_ids[lo];
+        const int64_t inner_pos = ids ? (int64_t)ids[e - s_pre[lo]] : -1;
+        const int64_t row = sub0 + lo, g = sub_base + (int64_t)e;
+        for (int k = 0; k < a.n_outer; ++k) {  // as stored: the derived plan keeps the column's descriptor
+          const int8_t* src = fc[a.outer_col[k]];
+          int8_t* dst = dc[a.outer_col[k]];
+          switch (a.outer_w[k]) {
+            case 1: dst[g] = src[row]; break;
+            case 2: ((int16_t*)dst)[g] = ((const int16_t*)src)[row]; break;
+            case 4: ((int32_t*)dst)[g] = ((const int32_t*)src)[row]; break;
+            default: ((int64_t*)dst)[g] = ((const int64_t*)src)[row];
+          }
+        }
+        for (int k = 0; k < a.n_inner; ++k) {
+          const int8_t* src = p.inner_cols[a.inner_col[k]];
+          int8_t* dst = dc[a.inner_dst[k]];
+          switch (a.inner_w[k]) {
+            case 1: dst[g] = inner_pos >= 0 ? src[inner_pos] : (int8_t)a.null_pat[k]; break;
+            case 2: ((int16_t*)dst)[g] = inner_pos >= 0 ? ((const int16_t*)src)[inner_pos] : (int16_t)a.null_pat[k]; break;
+            case 4: ((int32_t*)dst)[g] = inner_pos >= 0 ? ((const int32_t*)src)[inner_pos] : (int32_t)a.null_pat[k]; break;
+            default: ((int64_t*)dst)[g] = inner_pos >= 0 ? ((const int64_t*)src)[inner_pos] : a.null_pat[k];
+          }
+        }
+      }
+      sub_base += (int64_t)sub_total;
+      __syncthreads();  // (s_pre / s_ids / s_w are rewritten by the next sub-tile)
+    }
+  }
+}
+
 }  // namespace
 
 int64_t projection_tile_rows() { return kTileRows; }
@@ -1717,6 +1989,19 @@ hipError_t launch_projection_count_live(const int64_t* keys, int64_t stride_quad
   int64_t g = (entries + kBlock * 8 - 1) / (kBlock * 8);
   g = g < 1 ? 1 : g > 2048 ? 2048 : g;
   hipLaunchKernelGGL(k_proj_count_live, dim3((unsigned)g), dim3(kBlock), 0, s, keys, stride_quads, entries, d_count);
+  return hipGetLastError();
+}
+
+hipError_t launch_join_expand_count(const DevPlan& p, const JoinExpand& je, int n_cus, hipStream_t s) {
+  if (je.n_tiles > 0)
+    hipLaunchKernelGGL(k_join_expand_count, dim3((unsigned)std::min<int64_t>(je.n_tiles, (int64_t)n_cus * 8)), dim3(kBlock), 0, s, p, je);
+  hipLaunchKernelGGL(k_join_expand_scan, dim3(1), dim3(1024), 0, s, je);  // (no tiles: the fragments' totals are zeros)
+  return hipGetLastError();
+}
+
+hipError_t launch_join_expand_write(const DevPlan& p, const JoinExpand& je, int n_cus, hipStream_t s) {
+  if (je.pass_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_join_expand_write, dim3((unsigned)std::min<int64_t>(je.pass_tiles, (int64_t)n_cus * 8)), dim3(kBlock), 0, s, p, je);
   return hipGetLastError();
 }
 

@@ -584,6 +584,10 @@ typedef struct mi355q_exec_options {
                                             per 128-byte segment, instead of the packed ones (8-byte value, 16-bit entry
                                             inside the unit, twelve per segment; tests and bench.py --opt-flags compare
                                             the two) */
+#define MI355Q_OPT_NO_JOIN_EXPAND 32768u  /* grouped steps over a one-to-many join table: the row kernel (probe and group
+                                            update per joined row) even where the joined rows would be laid down as dense
+                                            columns (k_join_expand) for a step without the join (tests and
+                                            tools/join_expand_bench.py compare the two) */
 
 /* per-call timing/selection report (what launchGpuCode logs,
  * QueryExecutionContext.cpp:334,364,579) */

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "fast_common.h"
+#include "lattice_index.h"
 #include "part_host.h"
 
 namespace mq {
@@ -238,35 +239,9 @@ struct ScatterArgs {
   int32_t val_nullable;
   int64_t null_bits;
   int64_t kmin;         // DIRECT partitioning (join probes): partition = (key - kmin) / S1; LATTICE: the first lattice point
-  // LATTICE (MODE 3): key = kmin + lat_stride x idx with idx < lat_card; lat_rcp = floor(2^64 / lat_stride) (lat_stride >= 2)
-  uint64_t lat_stride, lat_rcp, lat_card;
+  // LATTICE (MODE 3 / 4): key = kmin + lat.stride x idx with idx < lat.card, found by exact division (lattice_index.h)
+  LatticeDiv lat;
 };
-
-// idx = (key - kmin) / stride through the plan-time reciprocal: mulhi(d, floor(2^64 / s)) is floor(d / s) or one less
-// (d / s - d x floor(2^64 / s) / 2^64 < d / 2^64 < 1 — the argument of HomeMap), so one conditional step makes quotient and
-// remainder exact.  true = the key is a lattice point of the range: remainder 0 and idx < card (a key below kmin wraps to
-// a d beyond the range, so its idx is >= card as well).
-MQ_D uint64_t mulhi_u64(uint64_t a, uint64_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __umul64hi(a, b);
-#else
-  return (uint64_t)(((unsigned __int128)a * b) >> 64);
-#endif
-}
-MQ_D bool lattice_index(const ScatterArgs& g, int64_t key, uint64_t* idx) {
-  const uint64_t d = (uint64_t)key - (uint64_t)g.kmin;
-  uint64_t q = d, r = 0;
-  if (g.lat_stride > 1) {
-    q = mulhi_u64(d, g.lat_rcp);
-    r = d - q * g.lat_stride;
-    if (r >= g.lat_stride) {
-      r -= g.lat_stride;
-      ++q;
-    }
-  }
-  *idx = q;
-  return r == 0 && q < g.lat_card;
-}
 
 // Packed records of the lattice member.  A record of partition idx mod P only needs e = idx / P, the entry inside the
 // unit, and the member runs only where a unit's entries fit its LDS table (<= 150 KB / 4 = 38 400), so e fits 16 bits by
@@ -514,7 +489,10 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
   if (wave < kProdWaves) {
     // ------------------------------------------------------------------ producers
     constexpr int64_t kSuperQuads = (int64_t)kProdWaves * 64;  // quads per workgroup step
-    int64_t c_key[4], c_val[4];
+    // what a record carries next to its value: the key (DIRECT, MODE 2), its kid, or — 32 bits — its lattice index / entry
+    using RK = typename std::conditional<LATTICE, uint32_t, int64_t>::type;
+    RK c_key[4];
+    int64_t c_val[4];
     uint32_t c_pid[4], c_slot[4];
     uint32_t c_mask = 0;
     uint32_t tile_no = 0;
@@ -533,7 +511,10 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
     };
     auto quad_of = [&]() -> int64_t { return (gt - base) * kSuperQuads + wave * 64 + lane; };
     // stage one record if its line is open; true = the record has left this lane
-    auto try_stage = [&](int64_t key, int64_t vb, uint32_t p, uint32_t s) -> bool {
+    // (LDS addresses as 32-bit byte offsets from smem_raw: 64-bit pointer arithmetic costs a quarter-rate multiply-add and
+    // two 64-bit shifts per record here)
+    const uint32_t lgLineBytes = (uint32_t)lgL + 4;  // a partition's line: L records of 16 bytes
+    auto try_stage = [&](RK key, int64_t vb, uint32_t p, uint32_t s) -> bool {
       if (PACK) {
         // segment q of the open line, position off - 12 q in it; the value with one 8-byte store, e with a 16-bit store of
         // its own (never a read-modify-write of the word: another producer fills the other half at the same time)
@@ -541,17 +522,20 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
         if (off >= line_recs) return false;
         asm volatile("" ::: "memory");
         const uint32_t q = div12_small(off);
-        char* seg = (char*)(stage + ((size_t)p << lgL) + (q << 3));
+        const uint32_t seg = (p << lgLineBytes) + (q << 7);
         const uint32_t u = off - q * kPackRecs;
-        ((int64_t*)seg)[u] = vb;
-        ((uint16_t*)(seg + kPackEntryOff))[u] = (uint16_t)key;
+        *(int64_t*)(smem_raw + (seg + (u << 3))) = vb;
+        *(uint16_t*)(smem_raw + (seg + kPackEntryOff + (u << 1))) = (uint16_t)key;
         asm volatile("" ::: "memory");
         atomicAdd(&written[p], 1u);
         return true;
       }
       if (lds_peek(&flushed[p]) != (s >> lgL)) return false;
       asm volatile("" ::: "memory");  // compiler order only: the LDS itself runs a wave in order
-      stage[((size_t)p << lgL) + (s & Lm1)] = Rec{key, vb};
+      // (the other members keep the 64-bit form: they sit at 127 - 128 VGPRs, and with the 32-bit one the allocator spills
+      // more of <long, long> and <long, double>, MODE 0: 20 -> 36 bytes of scratch a lane)
+      if (LATTICE) *(Rec*)(smem_raw + ((p << lgLineBytes) + ((s & Lm1) << 4))) = Rec{(int64_t)key, vb};
+      else stage[((size_t)p << lgL) + (s & Lm1)] = Rec{(int64_t)key, vb};
       asm volatile("" ::: "memory");
       atomicAdd(&written[p], 1u);
       return true;
@@ -585,7 +569,8 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
       auto one_row = [&](int i, auto hot_aware) {
         bool park = false;
         uint32_t p = 0, s = 0;
-        int64_t vb = 0, rk = 0;  // rk: what the record carries — the key (DIRECT), its kid, its lattice index or (PACK) entry
+        int64_t vb = 0;
+        RK rk = 0;  // what the record carries — the key (DIRECT), its kid, its lattice index or (PACK) entry
         if (i < cur.valid && filter_pass_narrow<FT>(flt, quad_get(cur.f, i)) &&
             (!DIRECT || (uint64_t)cur.k.v[i] - (uint64_t)g.kmin < (uint64_t)g.hm.d)) {
           const int64_t key = cur.k.v[i];
@@ -619,16 +604,16 @@ __global__ __launch_bounds__(kPartBlock) void k_part_scatter(
           }
           bool on_lattice = true;
           if (LATTICE && !folded) {
-            uint64_t idx;
-            on_lattice = lattice_index(g, key, &idx);
+            uint32_t idx;
+            on_lattice = lattice_index(g.lat, (uint64_t)key - (uint64_t)g.kmin, &idx);
             if (!on_lattice) atomicExch(sl.d_err + 2, 1);
-            p = (uint32_t)idx & (uint32_t)(g.P - 1);
-            rk = PACK ? (int64_t)(idx >> lgP) : (int64_t)idx;
+            p = idx & (uint32_t)(g.P - 1);
+            rk = (RK)(PACK ? idx >> lgP : idx);
           }
           if (!folded && on_lattice) {
             if (!LATTICE) {
               p = part_of(g.hm, DIRECT ? (uint32_t)((uint64_t)key - (uint64_t)g.kmin) : home_from_hash(g.hm, h));
-              rk = MODE != 0 ? key : kid_of(key, h);
+              rk = (RK)(MODE != 0 ? key : kid_of(key, h));
             }
             // (the one key whose kid is the LDS tables' empty mark takes the spill list, like a record
             // that meets a full run)
@@ -2767,7 +2752,10 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
     const uint64_t card = ((uint64_t)p.key_rng_max - (uint64_t)kmin) / stride + 1;
     // (card reaches 2^64 - 1 for a range that spans the type: no rounding sum that could wrap)
     const uint64_t per_unit = card / (uint64_t)h.g.P + (card % (uint64_t)h.g.P ? 1 : 0);
-    if (per_unit > lat.e_fit) {
+    // (the exact-division index is 32 bits: more points than that never fit the units' tables either — per_unit <= e_fit
+    // already says so, lattice_div_make says it in one comparison)
+    LatticeDiv div{};
+    if (!lattice_div_make(stride, card, &div) || per_unit > lat.e_fit) {
       if (trace) std::fprintf(stderr, "[mi355q] phase 2 member: k_part_aggregate (stride %llu: %llu lattice points, a unit's LDS table holds %u of %llu)\n",
                               stride, (unsigned long long)card, lat.e_fit, (unsigned long long)per_unit);
       return hipSuccess;
@@ -2790,9 +2778,7 @@ hipError_t launch_baseline_partitioned(const DevPlan& p, const FragView& fv, int
     const AggIdxKernel agg_idx = aggregate_idx_member(h.op_mask, lds2, pack);
     ScatterArgs sl3 = sa;
     sl3.kmin = kmin;
-    sl3.lat_stride = stride;
-    sl3.lat_rcp = stride > 1 ? (uint64_t)((((unsigned __int128)1) << 64) / stride) : 0;
-    sl3.lat_card = card;
+    sl3.lat = div;
     if (trace) std::fprintf(stderr, "[mi355q] phase 2 member: k_part_aggregate_idx (stride %llu, %llu lattice points, %d units of %u entries)\n",
                             stride, (unsigned long long)card, lg.P, lg.E);
     if (trace) std::fprintf(stderr, pack ? "[mi355q] lattice records: 12 per 128-byte segment (8-byte value, 16-bit entry)\n"

@@ -40,6 +40,19 @@ PROJECT = 101  # a Projection step's non-aggregate target (the value of a column
 COUNT_IF, SUM_IF = 10, 11
 # mi355q_join_kind
 JOIN_INNER, JOIN_LEFT = 0, 1
+
+
+def INNER_COL(i: int) -> int:
+    """MI355Q_INNER_COL: inner-table column i in quals[].col / group_cols[] of a join step"""
+    return 0x40000000 | i
+
+
+def IS_INNER_COL(c: int) -> bool:
+    return c >= 0x40000000
+
+
+def INNER_COL_INDEX(c: int) -> int:
+    return c & 0x3FFFFFFF
 # mi355q_desc_type
 GROUP_BY_PERFECT_HASH, GROUP_BY_BASELINE_HASH, NON_GROUPED_AGGREGATE = 0, 1, 4
 PROJECTION = 2
@@ -212,6 +225,7 @@ OPT_NO_AGG_PROGRAMS = 4096
 OPT_NO_GROUPED_AGG_PROGRAMS = 8192
 OPT_NO_LATTICE_PACK = 16384
 OPT_NO_JOIN_EXPAND = 32768   # grouped steps over a one-to-many join table stay in the row kernel (no k_join_expand)
+OPT_NO_STAR_GROUPBY = 65536  # star joins (INNER_COL): the flattened route even where k_star_groupby_lds would run
 
 
 class ExecReport(C.Structure):

@@ -128,8 +128,11 @@ int64_t mq::api::algorithmic_bytes(const mi355q_plan& p, const mi355q_inputs& in
     for (int i = 0; i < p.exprs[k].n_nodes && i < MI355Q_MAX_EXPR_NODES; ++i)
       if (p.exprs[k].nodes[i].op == MI355Q_EX_COL && p.exprs[k].nodes[i].arg >= 0 && p.exprs[k].nodes[i].arg < p.n_cols)
         used[p.exprs[k].nodes[i].arg] = true;
-  for (int i = 0; i < p.n_quals; ++i) used[p.quals[i].col] = true;
-  for (int g = 0; g < p.n_group_cols; ++g) used[p.group_cols[g]] = true;
+  // (an inner reference of the stated plan of a star join, execute_inner_refs' report: no outer column's bytes)
+  for (int i = 0; i < p.n_quals; ++i)
+    if (!MI355Q_IS_INNER_COL(p.quals[i].col)) used[p.quals[i].col] = true;
+  for (int g = 0; g < p.n_group_cols; ++g)
+    if (!MI355Q_IS_INNER_COL(p.group_cols[g])) used[p.group_cols[g]] = true;
   if (p.join_outer_col >= 0) {
     used[p.join_outer_col] = true;
     for (int i = 1; i < p.n_join_cols && i < MI355Q_MAX_GROUP_COLS; ++i) used[p.join_outer_cols[i]] = true;
@@ -228,6 +231,7 @@ int32_t mi355q_release_workspace(int32_t device_id) {
   ctx.wide.release();
   ctx.proj.release();
   ctx.gather.release();
+  ctx.star.release();
   ctx.lattice.release();
   if (ctx.bf_table) (void)hipFree(ctx.bf_table);
   ctx.bf_table = nullptr;
@@ -828,6 +832,8 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
   for (int i = 0; i < plan->n_quals && i < MI355Q_MAX_QUALS; ++i)
     if (MI355Q_QUAL_OR_GROUP(plan->quals[i].op) != 0) o.force_generic = 1;  // a disjunction among the quals: the row kernel
   set_step_knobs(o);
+  // ---- inner columns in the quals / group columns: the flattened plan's routes (the asynchronous call completes here)
+  if (plan->abi_version == MI355Q_ABI_VERSION && has_inner_refs(*plan)) return execute_inner_refs(plan, in, o, out, report, reserved);
   const bool async = pend != nullptr;
   if (async) {
     TuneKnobs k = tune_knobs();

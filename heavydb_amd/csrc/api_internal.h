@@ -144,6 +144,7 @@ struct DeviceCtx {
   Workspace wide;           // 8-byte-slot table of a step whose result layout has 4-byte slots
   Workspace proj;           // dense temporary columns of projected expressions (one pass of fragments)
   Workspace gather;         // dense temporary columns of a grouped join's inner side (execute_join_gather, and execute_join_expand's joined rows: the two never nest, their derived step has no join; may nest inside proj's step)
+  Workspace star;           // the slot -> group entry map of a star join (execute_inner_refs: k_join_group_code writes it, k_star_groupby_lds reads it)
   Workspace lattice;        // dense INT32 key columns of a lattice-keyed step (execute_affine_twin; may nest inside both)
   void* bf_table = nullptr; // a compiled filter in device memory (boolfilter.h BoolFilter: atoms + truth table)
   Workspace maskws;         // the row mask of a compiled filter with program atoms (execute_masked: one pass of fragments)
@@ -364,6 +365,10 @@ int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, co
                             const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_join_expand(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
                             const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
+// (inner columns in a join step's quals / group columns: asked ahead of every other route, and answers for good — the
+// gather / expand routes above over the flattened plan; no other route meets an inner reference)
+int32_t execute_inner_refs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
+                           mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_perfect_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
                              int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_affine_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,

@@ -12,6 +12,7 @@
 
 #include "api_internal.h"
 #include "boolfilter.h"
+#include "lds_args.h"
 
 namespace mq {
 namespace api {
@@ -636,72 +637,43 @@ int32_t execute_multi_value(const mi355q_plan* plan, const mi355q_inputs* in, co
 // row multiplicity: execute_join_expand below.  kNotTaken when the shape does not call for it.
 int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
                             const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  if (plan->join_outer_col < 0 || plan->n_group_cols < 1 || plan->n_exprs != 0 || o.kernel_variant == 1 || o.force_generic ||
-      (d.join_hash_type != 0 && d.join_hash_type != 1) || q.desc_type == MI355Q_NON_GROUPED_AGGREGATE)
+  // a plan with inner references (execute_inner_refs) has no row-kernel alternative: every input size, non-grouped aggregate
+  // steps and forced variants too; `q` is its flattened plan's descriptor, `d` carries the join alone
+  const bool refs = has_inner_refs(*plan);
+  if (plan->join_outer_col < 0 || plan->n_exprs != 0 || (d.join_hash_type != 0 && d.join_hash_type != 1)) return kNotTaken;
+  if (!refs && (plan->n_group_cols < 1 || o.kernel_variant == 1 || o.force_generic || q.desc_type == MI355Q_NON_GROUPED_AGGREGATE))
     return kNotTaken;
   const int nc = plan->n_cols, nf = in->n_frags;
   const bool inner_join = plan->join_kind != MI355Q_JOIN_LEFT;
   int64_t total_rows = 0, max_frag_rows = 0;
   if (frag_row_totals(*in, &total_rows, &max_frag_rows)) return kNotTaken;  // (a negative count: the plain step's to refuse)
   // (kernel_variant 2 = "the large-input members": how the tests reach this route with small tables)
-  if (nf < 1 || (o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
+  if (nf < 1 || (!refs && o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
   // a perfect-hash table of <= 64 KB is aggregated by the row kernel in a per-workgroup LDS copy (launch_generic): probe and
   // update in one pass, nothing gained by splitting them — measured at 1 B rows, 100 groups: 49 ms there, 57 ms here; 10 000
   // groups (global atomics there): 470 / 163 ms there (LEFT / INNER), 69 / 64 ms here (profiles/r04_grouped_join_1b_call16/17.jsonl)
-  if (o.kernel_variant != 2 && q.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && q.entry_count * (int64_t)q.row_size <= 64 * 1024)
+  if (!refs && o.kernel_variant != 2 && q.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && q.entry_count * (int64_t)q.row_size <= 64 * 1024)
     return kNotTaken;
-  // the inner columns the targets read, in order of first use
-  int32_t used[MI355Q_MAX_COLS], dst[MI355Q_MAX_COLS], width[MI355Q_MAX_COLS];
+  // the inner columns the plan reads as outer columns behind the stated ones (+ the matched flag): plan.cpp flatten_inner_refs
+  mi355q_plan p2;
+  InnerFlat fl;
+  if (int32_t e = flatten_inner_refs(*plan, true, &p2, &fl)) return refs ? e : kNotTaken;
+  const int n_used = fl.n_inner, flag_col = fl.flag_col, nc2 = p2.n_cols;
+  const int32_t* used = fl.inner_col;
+  int32_t dst[MI355Q_MAX_COLS], width[MI355Q_MAX_COLS];
   int64_t null_pat[MI355Q_MAX_COLS];
-  int n_used = 0;
-  mi355q_plan p2 = *plan;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const mi355q_target& tg = plan->targets[t];
-    if (tg.agg == MI355Q_PROJECT_KEY || tg.table == 0 || tg.col < 0) continue;
-    if (tg.col >= plan->n_inner_cols) return kNotTaken;
-    int j = 0;
-    while (j < n_used && used[j] != tg.col) ++j;
-    if (j == n_used) {
-      const mi355q_col_desc& cd = plan->inner_cols[tg.col];
-      if (cd.encoding != MI355Q_ENC_NONE || (cd.logical_type != 0 && cd.logical_type != cd.type)) return kNotTaken;
-      if (nc + n_used + 1 + (inner_join ? 1 : 0) > MI355Q_MAX_COLS) return kNotTaken;
-      used[n_used] = tg.col;
-      dst[n_used] = nc + n_used;
-      width[n_used] = plain_width(cd.type);
-      null_pat[n_used] = cd.type == MI355Q_DOUBLE ? kNullDoubleBits
-                         : cd.type == MI355Q_FLOAT ? (int64_t)(uint32_t)kNullFloatBits : plain_int_null(cd.type);
-      p2.cols[nc + n_used] = cd;
-      // (nullable under an outer join, resolve_targets' rule; the RANGE stays the column's own, as the layout decisions read it)
-      if (!inner_join) p2.cols[nc + n_used].nullable = 1;
-      p2.col_ranges[nc + n_used] = plan->inner_col_ranges[tg.col];
-      ++n_used;
-    }
-    p2.targets[t].table = 0;
-    p2.targets[t].col = nc + j;
+  for (int j = 0; j < n_used; ++j) {
+    const mi355q_col_desc& cd = plan->inner_cols[used[j]];
+    dst[j] = nc + j;
+    width[j] = plain_width(cd.type);
+    null_pat[j] = cd.type == MI355Q_DOUBLE ? kNullDoubleBits
+                  : cd.type == MI355Q_FLOAT ? (int64_t)(uint32_t)kNullFloatBits : plain_int_null(cd.type);
   }
-  int flag_col = -1;
-  if (inner_join) {
-    if (plan->n_quals >= MI355Q_MAX_QUALS) return kNotTaken;
-    flag_col = nc + n_used;
-    p2.cols[flag_col] = mi355q_col_desc{MI355Q_INT32, 0, MI355Q_ENC_NONE, 0};  // (INT32: the fast families' range filters read INT32 / INT64)
-    p2.col_ranges[flag_col] = mi355q_range{1, 0, 0, 1, 0.0, 0.0, 0};
-    mi355q_qual& mq = p2.quals[p2.n_quals++];
-    mq = mi355q_qual{};
-    mq.col = flag_col;
-    mq.op = MI355Q_EQ;
-    mq.ival = 1;
-  }
-  const int nc2 = nc + n_used + (inner_join ? 1 : 0);
-  p2.n_cols = nc2;
-  p2.join_outer_col = -1;
-  p2.join_table = nullptr;
-  p2.n_join_cols = 0;
-  p2.join_kind = MI355Q_JOIN_INNER;
-  p2.n_inner_cols = 0;
   mi355q_qmd q2;
   if (qmd_init(p2, &q2) != MI355Q_OK || std::memcmp(&q, &q2, sizeof(q)) != 0) return kNotTaken;  // the same layout, or not this way
   if (reserved) {
-    route_note("k_join_gather (inner columns + matched flag as outer columns)");
+    route_note(refs ? "inner columns flattened: k_join_gather (inner columns + matched flag as outer columns)"
+                    : "k_join_gather (inner columns + matched flag as outer columns)");
     // the derived step's shape: the same fragments with nc2 columns (the pointers are not looked at in reserve mode)
     std::vector<const void*> fake((size_t)nf * nc2, nullptr);
     mi355q_inputs in2 = *in;
@@ -742,9 +714,11 @@ int32_t execute_join_gather(const mi355q_plan* plan, const mi355q_inputs* in, co
 // for it.
 int32_t execute_join_expand(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
                             const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
-  if (plan->join_outer_col < 0 || plan->n_group_cols < 1 || plan->n_exprs != 0 || o.kernel_variant == 1 || o.force_generic ||
-      (o.flags & MI355Q_OPT_NO_JOIN_EXPAND) || (d.join_hash_type != 2 && d.join_hash_type != 3) ||
-      q.desc_type == MI355Q_NON_GROUPED_AGGREGATE)
+  // (a plan with inner references: as in execute_join_gather — the route at every size, whatever the options say)
+  const bool refs = has_inner_refs(*plan);
+  if (plan->join_outer_col < 0 || plan->n_exprs != 0 || (d.join_hash_type != 2 && d.join_hash_type != 3)) return kNotTaken;
+  if (!refs && (plan->n_group_cols < 1 || o.kernel_variant == 1 || o.force_generic || (o.flags & MI355Q_OPT_NO_JOIN_EXPAND) ||
+                q.desc_type == MI355Q_NON_GROUPED_AGGREGATE))
     return kNotTaken;
   const int nc = plan->n_cols, nf = in->n_frags;
   const bool left = plan->join_kind == MI355Q_JOIN_LEFT;
@@ -754,49 +728,31 @@ int32_t execute_join_expand(const mi355q_plan* plan, const mi355q_inputs* in, co
   // which the large-input families are planned at all, and the perfect-hash table the row kernel aggregates in a
   // per-workgroup LDS copy (launch_generic).  (kernel_variant 2 = "the large-input members": how the tests reach this route
   // with small tables)
-  if (nf < 1 || (o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
-  if (o.kernel_variant != 2 && q.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && q.entry_count * (int64_t)q.row_size <= 64 * 1024)
+  if (nf < 1 || (!refs && o.kernel_variant != 2 && total_rows < kIdxPartMinRows)) return kNotTaken;
+  if (!refs && o.kernel_variant != 2 && q.desc_type == MI355Q_GROUP_BY_PERFECT_HASH && q.entry_count * (int64_t)q.row_size <= 64 * 1024)
     return kNotTaken;
-  // the inner columns the targets read, in order of first use: plain columns, appended behind the stated ones
+  // the inner columns the plan reads: plain columns, appended behind the stated ones (plan.cpp flatten_inner_refs; no
+  // matched flag: an unmatched row of an INNER join has no joined row)
   JoinExpand je{};
   int32_t width[MI355Q_MAX_COLS];
-  mi355q_plan p2 = *plan;
-  for (int t = 0; t < plan->n_targets; ++t) {
-    const mi355q_target& tg = plan->targets[t];
-    if (tg.agg == MI355Q_PROJECT_KEY || tg.table == 0 || tg.col < 0) continue;
-    if (tg.col >= plan->n_inner_cols) return kNotTaken;
-    int j = 0;
-    while (j < je.n_inner && je.inner_col[j] != tg.col) ++j;
-    if (j == je.n_inner) {
-      const mi355q_col_desc& cd = plan->inner_cols[tg.col];
-      if (cd.encoding != MI355Q_ENC_NONE || (cd.logical_type != 0 && cd.logical_type != cd.type)) return kNotTaken;
-      if (nc + je.n_inner + 1 > MI355Q_MAX_COLS) return kNotTaken;
-      je.inner_col[j] = tg.col;
-      je.inner_dst[j] = nc + j;
-      je.inner_w[j] = width[j] = plain_width(cd.type);
-      je.null_pat[j] = cd.type == MI355Q_DOUBLE ? kNullDoubleBits
-                       : cd.type == MI355Q_FLOAT ? (int64_t)(uint32_t)kNullFloatBits : plain_int_null(cd.type);
-      p2.cols[nc + j] = cd;
-      // (nullable under an outer join, resolve_targets' rule; the RANGE stays the column's own, as the layout decisions read it)
-      if (left) p2.cols[nc + j].nullable = 1;
-      p2.col_ranges[nc + j] = plan->inner_col_ranges[tg.col];
-      ++je.n_inner;
-    }
-    p2.targets[t].table = 0;
-    p2.targets[t].col = nc + j;
+  mi355q_plan p2;
+  InnerFlat fl;
+  if (int32_t e = flatten_inner_refs(*plan, false, &p2, &fl)) return refs ? e : kNotTaken;
+  je.n_inner = fl.n_inner;
+  for (int j = 0; j < fl.n_inner; ++j) {
+    const mi355q_col_desc& cd = plan->inner_cols[fl.inner_col[j]];
+    je.inner_col[j] = fl.inner_col[j];
+    je.inner_dst[j] = nc + j;
+    je.inner_w[j] = width[j] = plain_width(cd.type);
+    je.null_pat[j] = cd.type == MI355Q_DOUBLE ? kNullDoubleBits
+                     : cd.type == MI355Q_FLOAT ? (int64_t)(uint32_t)kNullFloatBits : plain_int_null(cd.type);
   }
-  const int nc2 = nc + je.n_inner;
-  p2.n_cols = nc2;
-  p2.join_outer_col = -1;
-  p2.join_table = nullptr;
-  p2.n_join_cols = 0;
-  p2.join_kind = MI355Q_JOIN_INNER;
-  p2.n_inner_cols = 0;
+  const int nc2 = p2.n_cols;
   mi355q_qmd q2;
   if (qmd_init(p2, &q2) != MI355Q_OK || std::memcmp(&q, &q2, sizeof(q)) != 0) return kNotTaken;  // the same layout, or not this way
   if (reserved) {
     // nothing is launched, so no count exists: the derived step over the OUTER fragments' shape (the pointers are not looked at)
-    route_note("k_join_expand (joined rows as dense columns)");
+    route_note(refs ? "inner columns flattened: k_join_expand (joined rows as dense columns)" : "k_join_expand (joined rows as dense columns)");
     std::vector<const void*> fake((size_t)nf * nc2, nullptr);
     mi355q_inputs in2 = *in;
     in2.col_buffers = fake.data();
@@ -914,6 +870,142 @@ int32_t execute_join_expand(const mi355q_plan* plan, const mi355q_inputs* in, co
   if (int32_t e = rs.finish(report, pl.acc, 2, *plan, *in, total_rows)) return e;  // (+ 2: count and scan)
   *out = pl.res.release();
   return MI355Q_OK;
+}
+
+// The star member behind execute_inner_refs: few groups keyed by dimension attributes, a one-to-one perfect join table over one
+// INT32 / INT64 key (lds_args.h make_star_args states the rest).  k_join_group_code maps every join-table slot to its group's
+// entry — a dimension-sized pass, once per step, the map is not kept with the join table — and k_star_groupby_lds aggregates the
+// fact rows through it: no temporary column.  By default for maps up to kStarDefaultMapBytes16 / 32; kernel_variant 2 takes it at
+// every map size, MI355Q_OPT_NO_STAR_GROUPBY never.  kNotTaken: the flattened route runs the step.
+int32_t execute_star_groupby(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
+                             const DevPlan& d, int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved) {
+  if ((o.flags & MI355Q_OPT_NO_STAR_GROUPBY) || o.force_generic || o.kernel_variant == 1 || in->n_frags < 1 || d.join_hash_type != 0 ||
+      d.join_n_keys != 1 || q.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || q.output_columnar || q.slot_width != 8 ||
+      plan->n_group_cols < 1 || !d.join_buf || d.join_max < d.join_min || d.join_max - d.join_min + 1 != d.join_entries)
+    return kNotTaken;
+  for (int g = 0; g < plan->n_group_cols; ++g)
+    if (!MI355Q_IS_INNER_COL(plan->group_cols[g])) return kNotTaken;
+  for (int t = 0; t < plan->n_targets; ++t)
+    if (plan->targets[t].agg != MI355Q_PROJECT_KEY && plan->targets[t].table != 0) return kNotTaken;
+  StarStep st{};
+  mi355q_plan fp;
+  InnerFlat fl;
+  if (flatten_inner_refs(*plan, false, &fp, &fl) != MI355Q_OK) return kNotTaken;
+  if (build_dev_plan(fp, q, &st.flat) != MI355Q_OK) return kNotTaken;  // (the stated layout over the flattened plan's columns)
+  st.nc = plan->n_cols;
+  st.n_inner = fl.n_inner;
+  st.left = plan->join_kind == MI355Q_JOIN_LEFT;
+  st.key_col = d.join_cols[0];
+  const mi355q_col_desc& kd = plan->cols[st.key_col];
+  if (kd.encoding != MI355Q_ENC_NONE || (kd.logical_type != 0 && kd.logical_type != kd.type)) return kNotTaken;
+  st.key_type = kd.type;
+  st.key_nullable = kd.nullable != 0;
+  for (int j = 0; j < fl.n_inner; ++j) {
+    st.inner_col[j] = fl.inner_col[j];
+    st.inner_type[j] = plan->inner_cols[fl.inner_col[j]].type;
+    st.inner_base[j] = d.inner_cols[fl.inner_col[j]];
+    if (!reserved && !st.inner_base[j]) return kNotTaken;
+  }
+  st.inner_rows = in->inner_num_rows;
+  st.table = (const int32_t*)d.join_buf;
+  st.key_min = d.join_min;
+  st.n_slots = d.join_entries;
+  int64_t total_rows = 0, max_frag_rows = 0;
+  if (frag_row_totals(*in, &total_rows, &max_frag_rows)) return kNotTaken;
+  FragView fv{nullptr, nullptr, in->col_buffers, in->num_rows, in->n_frags, plan->n_cols, total_rows, max_frag_rows};
+  int64_t map_bytes = 0;
+  if (!star_groupby_eligible(st, fv, n_cus, &map_bytes)) return kNotTaken;
+  // the default per (code width, map size) class, as measured (lds_args.h); beyond it: kernel_variant 2
+  if (o.kernel_variant != 2 && map_bytes > (q.entry_count <= 32767 ? kStarDefaultMapBytes16 : kStarDefaultMapBytes32)) return kNotTaken;
+  if (reserved) {
+    route_note("k_join_group_code + k_star_groupby_lds");
+    *reserved = 0;
+    return MI355Q_OK;
+  }
+  RouteScope rs(in->device_id, o.stream);
+  if (rs.status) return rs.status;
+  hipStream_t s = rs.s;
+  if (const hipError_t he = rs.ctx.star.grow(map_bytes)) {
+    last_hip_error = he;
+    (void)hipGetLastError();
+    return kNotTaken;  // (the flattened route sizes its passes from what is free)
+  }
+  mi355q_result* res = nullptr;
+  if (int32_t e = result_create_impl(&q, in->device_id, o.out_buffer, &res)) return e;
+  ResultPtr owned(res);
+  FragTable ft;
+  if (int32_t e = upload_frag_table(rs.ctx, *in, plan->n_cols, s, FragUpload::kAlways, &ft)) return e;
+  UploadGuard upload_guard{s, true};
+  fv.d_cols = ft.d_cols;
+  fv.d_num_rows = ft.d_rows;
+  if (int32_t e = rs.begin_timing(report)) return e;
+  HIP_TRY(launch_init_buffer(res->buf, q.entry_count, make_row_init(q), s));
+  LaunchStats ls;
+  HIP_TRY(launch_star_groupby(st, fv, rs.ctx.star.p, res->buf, ft.d_err, n_cus, s, &ls));
+  mi355q_exec_report acc{};
+  std::snprintf(acc.kernel_name, sizeof(acc.kernel_name), "%s", ls.kernel_name);
+  acc.variant = ls.variant;
+  acc.n_launches = ls.n_launches;
+  if (int32_t e = rs.finish(report, acc, 0, *plan, *in, total_rows, ft.d_err)) return e;  // (synchronises: the upload has landed)
+  upload_guard.armed = false;
+  if (report) report->kernel_ms = report->total_ms;  // (map + scan: the step has no other launch)
+  *out = owned.release();
+  return MI355Q_OK;
+}
+
+// Star joins: a join step whose quals / group columns name INNER columns (MI355Q_INNER_COL, include/mi355q.h:
+// `SELECT d.region, COUNT(*), SUM(f.amount) FROM fact f JOIN dim d ON f.did = d.id WHERE d.segment BETWEEN 2 AND 5 GROUP BY
+// d.region`).  The step means what its flattened plan (plan.cpp flatten_inner_refs) means over the joined rows, and that is
+// how it runs: k_join_gather (one-to-one tables) or k_join_expand (one-to-many) lay the inner columns down as dense outer
+// columns and the flattened, joinless plan runs over them — at every input size and for non-grouped aggregates too, there
+// being no row-kernel alternative.  Asked ahead of every other route; never kNotTaken.  The star member
+// (execute_star_groupby above) is asked first.
+int32_t execute_inner_refs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
+                           mi355q_exec_report* report, int64_t* reserved) {
+  mi355q_plan flat;
+  InnerFlat fl;
+  if (int32_t e = flatten_inner_refs(*plan, true, &flat, &fl)) return e;
+  mi355q_qmd q;
+  if (int32_t e = qmd_init(flat, &q)) return e;
+  // the layout twins first, as in execute_impl: they run the same plan with another hint and come back here
+  if (q.output_columnar) return execute_columnar_twin(plan, in, o, q, out, report, reserved);
+  if (q.slot_width == 4) return execute_wide_slot_twin(plan, in, o, q, out, report, reserved);
+  // the join as the device sees it: a carrier plan that keeps the stated columns and the join and nothing else
+  mi355q_plan cp = *plan;
+  cp.n_quals = 0;
+  cp.n_group_cols = 0;
+  cp.n_targets = 1;
+  cp.targets[0] = mi355q_target{};
+  cp.targets[0].agg = MI355Q_COUNT;
+  cp.targets[0].col = -1;
+  cp.output_columnar_hint = MI355Q_OUTPUT_ROWWISE;
+  mi355q_qmd cq;
+  if (int32_t e = qmd_init(cp, &cq)) return e;
+  DevPlan d;
+  if (int32_t e = build_dev_plan(cp, cq, &d)) return e;
+  if (int32_t e = attach_join(cp, in, &d)) return e;
+  for (int j = 0; j < fl.n_inner; ++j)
+    if (!reserved && !d.inner_cols[fl.inner_col[j]] && in->inner_num_rows > 0) return MI355Q_ERR_INVALID_PLAN;
+  int n_cus = 0;
+  {
+    DeviceGuard g(in->device_id);
+    if (!g.ok) return MI355Q_ERR_HIP;
+    n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
+  }
+  int64_t total_rows = 0, max_frag_rows = 0;
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
+  if (total_rows == 0) {  // nothing to join: the flattened plan over no fragments, for the stated, initialised layout
+    mi355q_inputs in0 = *in;
+    in0.n_frags = 0;
+    in0.inner_col_buffers = nullptr;
+    return execute_impl(&flat, &in0, &o, out, report, nullptr, reserved);
+  }
+  const bool one_to_one = d.join_hash_type == 0 || d.join_hash_type == 1;
+  if (const int32_t es = try_route(out, [&] { return execute_star_groupby(plan, in, o, q, d, n_cus, out, report, reserved); }); es != kNotTaken)
+    return es;
+  const int32_t e = one_to_one ? execute_join_gather(plan, in, o, q, d, n_cus, out, report, reserved)
+                               : execute_join_expand(plan, in, o, q, d, n_cus, out, report, reserved);
+  return e == kNotTaken ? MI355Q_ERR_UNSUPPORTED : e;
 }
 
 // Baseline steps over 2 - 3 plain INT key columns that all have ranges — the reference's PerfectHashMultiCol / MultiStep

@@ -427,6 +427,17 @@ bool lds_groupby_prog_eligible(const DevPlan& p, const AggProgArgs& ap, const Fr
 hipError_t launch_lds_groupby_prog(const DevPlan& p, const AggProgArgs& ap, const FragView& fv, int64_t* out, int32_t* d_err,
                                    int n_cus, hipStream_t s, LaunchStats* st);
 
+// Star joins: few groups keyed by DIMENSION attributes over a one-to-one perfect join table (lds_args.h StarStep, make_star_args;
+// kernels_lds.hip k_join_group_code + k_star_groupby_lds): 1 - 3 plain INT32 / INT64 inner key columns whose perfect-hash table
+// fits ONE LDS window, range quals on plain INT8 / INT32 / INT64 inner columns and on up to 2 plain INT32 / INT64 outer columns,
+// COUNT / SUM / MIN / MAX / AVG over up to 3 plain INT32 / INT64 / DOUBLE outer columns, 16-byte aligned outer chunks.
+// `code_map`: *map_bytes of device memory, written by the first kernel and read by the second.  d_err[0]: MI355Q_ERR_OUT_OF_SLOTS
+// for an attribute outside its declared range on a row the step counts.  variant 8: 2-byte codes, 9: 4-byte codes.
+struct StarStep;
+bool star_groupby_eligible(const StarStep& step, const FragView& fv, int n_cus, int64_t* map_bytes);
+hipError_t launch_star_groupby(const StarStep& step, const FragView& fv, void* code_map, int64_t* out, int32_t* d_err, int n_cus,
+                               hipStream_t s, LaunchStats* st);
+
 bool join_sum_eligible(const DevPlan& p, const FragView& fv);
 hipError_t launch_join_sum(const DevPlan& p, const FragView& fv, int64_t* out, int n_cus,
                            hipStream_t s, LaunchStats* st);

@@ -982,5 +982,62 @@ hipError_t launch_lds_groupby_prog(const DevPlan& p, const AggProgArgs& ap, cons
   return hipSuccess;
 }
 
+// ... and of the star member (k_join_group_code + k_star_groupby_lds): the member's own description decides who is eligible
+// (lds_args.h make_star_args); a launch gathers the inner columns of a fragment into temporary columns through the join
+// table — the column's NULL for the unmatched row a LEFT join keeps, an INNER join's unmatched rows left out — and runs the
+// flattened plan's row function over them.
+bool star_groupby_eligible(const StarStep& step, const FragView& fv, int n_cus, int64_t* map_bytes) {
+  StarCodeArgs c;
+  StarArgs a;
+  if (!make_star_args(step, fv, n_cus, tune_knobs().flags, &c, &a)) return false;
+  *map_bytes = star_map_bytes(c);
+  return true;
+}
+hipError_t launch_star_groupby(const StarStep& step, const FragView& fv, void* code_map, int64_t* out, int32_t* d_err, int n_cus,
+                               hipStream_t, LaunchStats* st) {
+  StarCodeArgs c;
+  StarArgs a;
+  if (!make_star_args(step, fv, n_cus, tune_knobs().flags, &c, &a) || !code_map) return hipErrorInvalidValue;
+  st->kernel_name = "k_star_groupby_lds";
+  st->n_launches = 2;
+  st->variant = a.code16 ? 8 : 9;
+  const auto null_of = [](int type) -> int64_t {
+    return type == MI355Q_DOUBLE ? kNullDoubleBits : plain_int_null(type);
+  };
+  for (int f = 0; f < fv.n_frags; ++f) {
+    const int8_t* const* fc = fv.d_cols + (size_t)f * fv.n_cols;
+    const int64_t n = fv.d_num_rows[f];
+    std::vector<std::vector<int64_t>> tmp((size_t)step.n_inner, std::vector<int64_t>((size_t)n + 1));
+    std::vector<const int8_t*> cols(fc, fc + fv.n_cols);
+    for (int j = 0; j < step.n_inner; ++j) cols.push_back((const int8_t*)tmp[(size_t)j].data());
+    for (int64_t pos = 0; pos < n; ++pos) {
+      const int64_t k = step.key_type == MI355Q_INT32 ? (int64_t)((const int32_t*)fc[step.key_col])[pos] : ((const int64_t*)fc[step.key_col])[pos];
+      int64_t row = -1;
+      if (!(step.key_nullable && k == plain_int_null(step.key_type)) && k >= step.key_min && k - step.key_min < step.n_slots)
+        row = step.table[k - step.key_min];
+      if (row >= step.inner_rows) row = -1;
+      if (row < 0 && !step.left) continue;
+      for (int j = 0; j < step.n_inner; ++j) {
+        const int w = plain_width(step.inner_type[j]);
+        int64_t v = null_of(step.inner_type[j]);
+        if (row >= 0) {
+          const int8_t* b = step.inner_base[j];
+          v = w == 1 ? (int64_t)b[row] : w == 2 ? (int64_t)((const int16_t*)b)[row] : w == 4 ? (int64_t)((const int32_t*)b)[row] : ((const int64_t*)b)[row];
+        }
+        int8_t* dst = (int8_t*)tmp[(size_t)j].data();
+        if (w == 1) dst[pos] = (int8_t)v;
+        else if (w == 2) ((int16_t*)dst)[pos] = (int16_t)v;
+        else if (w == 4) ((int32_t*)dst)[pos] = (int32_t)v;
+        else ((int64_t*)dst)[pos] = v;
+      }
+      if (const int32_t e = process_row<true>(step.flat, cols.data(), pos, out, nullptr)) {
+        atomicCAS(d_err, 0, e);
+        return hipSuccess;
+      }
+    }
+  }
+  return hipSuccess;
+}
+
 }  // namespace mq
 #endif

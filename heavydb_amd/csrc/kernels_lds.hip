@@ -1312,6 +1312,194 @@ __global__ __launch_bounds__(kLdsProgBlock) void k_groupby_lds_prog(const int8_t
   lds_flush_replica0<NK, NV, kLdsProgBlock>(smem, l, p, e_lo, t, out, d_err);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The star member (lds_args.h StarArgs / StarCodeArgs): GROUP BY dimension attributes over fact JOIN dim, one-to-one perfect
+// join table.
+// k_join_group_code: once per step, one lane per join-table slot.  An empty slot gets the step's `code_unmatched`; a row id
+// the inner quals reject kStarDrop; otherwise the perfect-hash entry index of the row's attributes (the arithmetic of
+// codegenPerfectHashFunction as k_groupby_lds does it, NULL keys translated), kStarBadKey for an attribute outside its
+// declared range.  A row id is never followed unless 0 <= id < inner_rows.
+__global__ __launch_bounds__(256) void k_join_group_code(StarCodeArgs a) {
+  const int64_t gsize = (int64_t)gridDim.x * 256;
+  for (int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x; slot < a.n_slots; slot += gsize) {
+    const int64_t row = (int64_t)a.table[slot];
+    int32_t code = a.code_unmatched;
+    if (row >= a.inner_rows) {
+      code = kStarDrop;  // (not a row of the dimension: a table built from other columns)
+    } else if (row >= 0) {
+      bool pass = true;
+#pragma unroll
+      for (int k = 0; k < MI355Q_MAX_QUALS; ++k) {
+        if (k >= a.n_flt) break;
+        const int8_t* b = a.flt_base[k];
+        const int t = a.flt_type[k];
+        const int64_t x = t == MI355Q_INT32 ? (int64_t)((const int32_t*)b)[row] : t == MI355Q_INT8 ? (int64_t)b[row] : ((const int64_t*)b)[row];
+        pass = pass && filter_pass<int64_t>(a.flt[k], x);
+      }
+      int64_t idx = 0;
+      bool in_range = true;
+#pragma unroll
+      for (int g = 0; g < kLdsKeys; ++g) {
+        if (g >= a.n_keys) break;
+        const bool k32 = a.key_type[g] == MI355Q_INT32;
+        int64_t k = k32 ? (int64_t)((const int32_t*)a.key_base[g])[row] : ((const int64_t*)a.key_base[g])[row];
+        if (a.key_translate[g] && k == (k32 ? (int64_t)INT32_MIN : INT64_MIN)) k = a.key_null_key[g];
+        const int64_t d = k - a.key_min[g];
+        in_range = in_range && d >= 0 && d < a.key_card[g];
+        idx += d * a.key_mul[g];
+      }
+      in_range = in_range && (uint64_t)idx < (uint64_t)a.entry_count;
+      code = !pass ? kStarDrop : in_range ? (int32_t)idx : kStarBadKey;
+    }
+    if (a.code16) ((int16_t*)a.code)[slot] = (int16_t)code;
+    else ((int32_t*)a.code)[slot] = code;
+  }
+}
+
+// k_star_groupby_lds: the hot scan — k_groupby_lds_prog's skeleton (512-lane workgroups, K replicas in dynamic LDS, lane l on
+// replica l % K, the fact columns as 16-byte non-temporal quads with every load of a step issued before the first value is
+// looked at, the outer range quals as a 4-bit pass mask, a fragment's last partial quad down the same path, the shared fold
+// and flush) with the evaluator replaced by ONE cached load per passing row: code[key - key_min].  A NULL key and a key
+// outside the join table's range get code_unmatched without touching the map.
+// KT: the join key column is INT64 (else INT32); NV / NF: value columns and outer filter columns this member holds registers for.
+static_assert(sizeof(StarArgs) + sizeof(DevPlan) <= 3968, "k_star_groupby_lds takes its arguments by value: the kernel argument segment holds 4 KB");
+template <bool KT, int NV, int NF>
+__global__ __launch_bounds__(kStarBlock) void k_star_groupby_lds(const int8_t* const* __restrict__ cols, const int64_t* __restrict__ num_rows,
+                                                                  int n_frags, int n_cols, StarArgs a, DevPlan p, int64_t* __restrict__ out,
+                                                                  int32_t* __restrict__ d_err) {
+  constexpr int NVA = NV > 0 ? NV : 1, NFA = NF > 0 ? NF : 1;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const LdsArgs& l = a.l;
+  const int t = threadIdx.x;
+  const uint32_t K = 1u << l.copies_lg;
+  const uint32_t ne = l.entries;
+  // ---- initialise every replica: counters 0, sums 0, min / max identities (as k_groupby_lds_prog)
+  for (uint32_t r = 0; r < K; ++r) {
+    char* rep = smem + (size_t)r * l.copy_bytes;
+    for (uint32_t e = t; e < ne; e += kStarBlock) {
+      ((uint32_t*)(rep + l.off_rows))[e] = 0;
+#pragma unroll
+      for (int c = 0; c < NV; ++c) {
+        if (c >= l.n_vals) break;
+        const LdsVal& v = l.v[c];
+        const bool fp = v.type == MI355Q_DOUBLE;
+        if (v.off_cnt >= 0) ((uint32_t*)(rep + v.off_cnt))[e] = 0;
+        if (v.off_sum >= 0) ((int64_t*)(rep + v.off_sum))[e] = 0;
+        if (v.off_min >= 0) ((int64_t*)(rep + v.off_min))[e] = fp ? 0x7ff0000000000000ll : INT64_MAX;
+        if (v.off_max >= 0) ((int64_t*)(rep + v.off_max))[e] = fp ? (int64_t)0xfff0000000000000ull : INT64_MIN;
+      }
+    }
+  }
+  volatile uint32_t* const s_full = (volatile uint32_t*)(smem + ((size_t)l.copy_bytes << l.copies_lg));  // (never set: no baseline member)
+  if (t == 0) *s_full = 0u;
+  __syncthreads();
+  char* const my_rep = smem + (size_t)((uint32_t)t & (K - 1)) * l.copy_bytes;
+  bool bad = false;
+  const int64_t null_key = KT ? INT64_MIN : (int64_t)INT32_MIN;
+
+  auto quad_rows = [&](const RawQ& kq, const RawQ (&vq)[NVA], const RawQ (&fq)[NFA], uint32_t valid) {
+    uint32_t pass = valid;
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+      if (k >= l.n_flt) break;
+      uint32_t m = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        m |= (filter_pass<int64_t>(l.flt[k], l.flt_type[k] == MI355Q_INT32 ? (int64_t)rawq_i32(fq[k], i) : rawq_i64(fq[k], i)) ? 1u : 0u) << i;
+      pass &= m;
+    }
+    // the four codes first (the gathers of a quad are in flight together), then the updates
+    int32_t code[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      code[i] = kStarDrop;
+      if (!((pass >> i) & 1u)) continue;
+      const int64_t k = KT ? rawq_i64(kq, i) : (int64_t)rawq_i32(kq, i);
+      const uint64_t slot = (uint64_t)(k - a.key_min);
+      code[i] = a.code_unmatched;
+      if (!(a.key_nullable && k == null_key) && slot < (uint64_t)a.n_slots)
+        code[i] = a.code16 ? (int32_t)((const int16_t*)a.code)[slot] : ((const int32_t*)a.code)[slot];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int32_t e = code[i];
+      if (e == kStarBadKey) bad = true;
+      if (e < 0 || (uint32_t)e >= ne) continue;
+      atomicAdd((uint32_t*)(my_rep + l.off_rows) + e, 1u);
+#pragma unroll
+      for (int c = 0; c < NV; ++c) {
+        if (c >= l.n_vals) break;
+        lds_update(my_rep, l.v[c], (uint32_t)e, l.v[c].type == MI355Q_INT32 ? (int64_t)rawq_i32(vq[c], i) : rawq_i64(vq[c], i));
+      }
+    }
+  };
+
+  const uint32_t stripe = blockIdx.x, n_stripes = gridDim.x;
+  for (int f = 0; f < n_frags; ++f) {
+    const int8_t* const* fc = cols + (size_t)f * n_cols;
+    const int64_t n = num_rows[f];
+    const int64_t nq = n >> 2;
+    const int64_t nq_all = (n + 3) >> 2;  // the fragment's quads, its last partial one included
+    const int64_t n_tiles = (nq_all + kStarBlock - 1) / kStarBlock;
+    const int8_t* const kbase = fc[a.key_col];
+    const int8_t *vbase[NVA], *fbase[NFA];
+#pragma unroll
+    for (int c = 0; c < NVA; ++c) vbase[c] = (c < NV && c < l.n_vals) ? fc[l.v[c].col] : nullptr;
+#pragma unroll
+    for (int k = 0; k < NFA; ++k) fbase[k] = (k < NF && k < l.n_flt) ? fc[l.flt[k].col] : nullptr;
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int64_t tl = (stripe + (int64_t)f * 7) % n_stripes; tl < n_tiles; tl += n_stripes) {
+      const int64_t q = tl * kStarBlock + t;
+      RawQ kq, vq[NVA], fq[NFA];
+      kq.lo = kq.hi = v4i32{0, 0, 0, 0};
+#pragma unroll
+      for (int c = 0; c < NVA; ++c) vq[c].lo = vq[c].hi = v4i32{0, 0, 0, 0};
+#pragma unroll
+      for (int k = 0; k < NFA; ++k) fq[k].lo = fq[k].hi = v4i32{0, 0, 0, 0};
+      if (q < nq) {  // every load of a step is issued before the first value is looked at
+        load_rawq(kbase, q, KT, kq);
+#pragma unroll
+        for (int c = 0; c < NV; ++c)
+          if (vbase[c]) load_rawq(vbase[c], q, l.v[c].type != MI355Q_INT32, vq[c]);
+#pragma unroll
+        for (int k = 0; k < NF; ++k)
+          if (fbase[k]) load_rawq(fbase[k], q, l.flt_type[k] != MI355Q_INT32, fq[k]);
+      } else if (q < nq_all) {  // (one lane per fragment: the partial quad's rows one by one; a row past the end repeats the last one)
+        const int left = (int)(n & 3);
+        auto gather = [&](const int8_t* base, bool w8, RawQ& r) {
+          int64_t v[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int64_t pos = (nq << 2) + (i < left ? i : left - 1);
+            v[i] = w8 ? load_one<int64_t>(base, pos) : (int64_t)load_one<int32_t>(base, pos);
+          }
+          if (w8) {
+            r.lo.x = (int)(uint32_t)v[0]; r.lo.y = (int)(uint32_t)((uint64_t)v[0] >> 32); r.lo.z = (int)(uint32_t)v[1]; r.lo.w = (int)(uint32_t)((uint64_t)v[1] >> 32);
+            r.hi.x = (int)(uint32_t)v[2]; r.hi.y = (int)(uint32_t)((uint64_t)v[2] >> 32); r.hi.z = (int)(uint32_t)v[3]; r.hi.w = (int)(uint32_t)((uint64_t)v[3] >> 32);
+          } else {
+            r.lo.x = (int)v[0]; r.lo.y = (int)v[1]; r.lo.z = (int)v[2]; r.lo.w = (int)v[3];
+          }
+        };
+        gather(kbase, KT, kq);
+#pragma unroll
+        for (int c = 0; c < NV; ++c)
+          if (vbase[c]) gather(vbase[c], l.v[c].type != MI355Q_INT32, vq[c]);
+#pragma unroll
+        for (int k = 0; k < NF; ++k)
+          if (fbase[k]) gather(fbase[k], l.flt_type[k] != MI355Q_INT32, fq[k]);
+      }
+      const uint32_t valid = q < nq ? 15u : q < nq_all ? (1u << (int)(n & 3)) - 1u : 0u;
+      if (valid) quad_rows(kq, vq, fq, valid);
+    }
+  }
+  if (bad) atomicCAS(d_err, 0, MI355Q_ERR_OUT_OF_SLOTS);
+  __syncthreads();
+  if (!lds_fold_replicas<NVA, kStarBlock>(smem, l, t, s_full, d_err)) return;
+  lds_flush_replica0<kLdsKeys, NVA, kStarBlock>(smem, l, p, 0u, t, out, d_err);
+}
+
 bool make_lds_args(const DevPlan& p, const FragView& fv, int n_cus, LdsArgs* out) {
   LdsArgs& a = *out;
   bool need[kLdsVals][4] = {};
@@ -1551,6 +1739,61 @@ hipError_t launch_lds_groupby_prog(const DevPlan& p, const AggProgArgs& ap, cons
     else MQ_LDS_PROG_LAUNCH(4, 2, 3, 3);
   }
 #undef MQ_LDS_PROG_LAUNCH
+  rec(st->k_stop, s);
+  return hipGetLastError();
+}
+
+bool star_groupby_eligible(const StarStep& step, const FragView& fv, int n_cus, int64_t* map_bytes) {
+  StarCodeArgs c;
+  StarArgs a;
+  if (!make_star_args(step, fv, n_cus, tune_knobs().flags, &c, &a)) return false;
+  *map_bytes = star_map_bytes(c);
+  return true;
+}
+
+hipError_t launch_star_groupby(const StarStep& step, const FragView& fv, void* code_map, int64_t* out, int32_t* d_err, int n_cus,
+                               hipStream_t s, LaunchStats* st) {
+  StarCodeArgs c;
+  StarArgs a;
+  if (!make_star_args(step, fv, n_cus, tune_knobs().flags, &c, &a) || !code_map) return hipErrorInvalidValue;
+  c.code = code_map;
+  a.code = code_map;
+  const LdsArgs& l = a.l;
+  const size_t lds = ((size_t)l.copy_bytes << l.copies_lg) + 16;  // + the fold's "a replica is full" word
+  st->kernel_name = "k_star_groupby_lds";
+  st->n_launches = 2;
+  st->variant = a.code16 ? 8 : 9;  // 8: 2-byte codes, 9: 4-byte codes
+  {
+    int64_t grid = (c.n_slots + 255) / 256;
+    if (grid > (int64_t)n_cus * 8) grid = (int64_t)n_cus * 8;
+    hipLaunchKernelGGL(k_join_group_code, dim3((unsigned)grid), dim3(256), 0, s, c);
+  }
+  int64_t want = ((fv.total_rows + 3) / 4 + kStarBlock - 1) / kStarBlock;
+  if (want < 1) want = 1;
+  const int grid = (int)std::min<int64_t>(n_cus > 0 ? n_cus : 1, want);
+  rec(st->k_start, s);
+#define MQ_STAR_LAUNCH(KT, NV, NF)                                                                                      \
+  do {                                                                                                                  \
+    auto k = k_star_groupby_lds<KT, NV, NF>;                                                                            \
+    const hipError_t ea = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
+    if (ea != hipSuccess) return ea;                                                                                    \
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kStarBlock), lds, s, fv.d_cols, fv.d_num_rows, fv.n_frags, fv.n_cols, a, step.flat, \
+                       out, d_err);                                                                                     \
+  } while (0)
+  // the smallest member that holds the step: (one value column | three) x (no outer filter column | two), per key width
+  const bool v1 = l.n_vals <= 1, f0 = l.n_flt == 0;
+  if (a.key_w8) {
+    if (v1 && f0) MQ_STAR_LAUNCH(true, 1, 0);
+    else if (v1) MQ_STAR_LAUNCH(true, 1, 2);
+    else if (f0) MQ_STAR_LAUNCH(true, 3, 0);
+    else MQ_STAR_LAUNCH(true, 3, 2);
+  } else {
+    if (v1 && f0) MQ_STAR_LAUNCH(false, 1, 0);
+    else if (v1) MQ_STAR_LAUNCH(false, 1, 2);
+    else if (f0) MQ_STAR_LAUNCH(false, 3, 0);
+    else MQ_STAR_LAUNCH(false, 3, 2);
+  }
+#undef MQ_STAR_LAUNCH
   rec(st->k_stop, s);
   return hipGetLastError();
 }

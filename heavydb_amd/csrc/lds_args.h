@@ -2,7 +2,9 @@
 // workgroup's LDS; kernels_idx.hip: perfect-hash tables too large for that, partitioned by entry index).
 #pragma once
 
+#include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "boolfilter.h"
 #include "fast_common.h"
@@ -311,5 +313,152 @@ inline bool make_lds_prog_args(const DevPlan& p, const AggProgArgs& ap, const Fr
   if (fv.total_rows / stripes >= 0xfff00000ll) return false;
   return true;
 }
+
+// ---- the star member (kernels_lds.hip k_join_group_code + k_star_groupby_lds; api_routes.cpp execute_inner_refs): a few-groups
+// GROUP BY keyed by DIMENSION attributes over fact JOIN dim with a one-to-one perfect join table.  k_join_group_code maps every
+// join-table slot to the entry index of its dimension row's group once per step; the hot scan then needs ONE gather per fact
+// row — code[key - min_key] — in place of the probe, the attribute loads and the perfect-hash arithmetic, and no temporary
+// column.  Codes: >= 0 the entry index; kStarDrop (-1) the row does not count (an inner qual rejects its dimension row, or, as
+// `code_unmatched` of an INNER join, it has none); kStarBadKey (-2) an attribute outside its declared range (the row raises
+// MI355Q_ERR_OUT_OF_SLOTS, as the family does for such a key).  An EMPTY slot of the join table holds the step's constant
+// `code_unmatched` itself — what a NULL fact key and a key outside [min_key, max_key] get without looking at the map: -1 for an
+// INNER join, and for a LEFT join the entry of the all-NULL key, or -1 where an inner qual is not TRUE for NULL.
+constexpr int kStarBlock = 512;
+constexpr int kStarOuterFlt = 2;           // outer columns under range quals
+constexpr int32_t kStarDrop = -1, kStarBadKey = -2;
+// maps up to here are planned by default; beyond, the member waits behind kernel_variant 2.  2-byte codes: MEASURED at 1 B rows
+// with maps of 0.2, 2 and 32 MB — the member beat the flattened route 3.5 - 7.7 x in every class (DESIGN 3.9,
+// profiles/star_join_bench_1b.jsonl); 4-byte codes (more than 32 767 entries) are UNMEASURED: one XCD's L2
+constexpr int64_t kStarDefaultMapBytes16 = (int64_t)32 << 20, kStarDefaultMapBytes32 = (int64_t)4 << 20;
+struct StarCodeArgs {                      // k_join_group_code
+  const int32_t* table;                    // the join table: row id per slot, < 0 = empty
+  int64_t n_slots, inner_rows;
+  int32_t n_keys, n_flt, code16, code_unmatched;
+  const int8_t* key_base[kLdsKeys];        // the inner key columns (plain INT32 / INT64)
+  int32_t key_type[kLdsKeys], key_translate[kLdsKeys];
+  int64_t key_min[kLdsKeys], key_card[kLdsKeys], key_mul[kLdsKeys], key_null_key[kLdsKeys];
+  const int8_t* flt_base[MI355Q_MAX_QUALS];  // the inner columns under range quals (plain INT8 / INT32 / INT64)
+  int32_t flt_type[MI355Q_MAX_QUALS];
+  RangeFilter flt[MI355Q_MAX_QUALS];
+  int64_t entry_count;
+  void* code;                              // int16 [n_slots] (code16) or int32 [n_slots]
+};
+struct StarArgs {                          // k_star_groupby_lds
+  LdsArgs l;                               // the table side: key_* (for the flush), v[], the replica layout; flt[0 .. n_flt): the OUTER range quals
+  int32_t key_col, key_w8, key_nullable, code16;  // the fact's join key column
+  int64_t key_min, n_slots;                // slot = key - key_min, 0 <= slot < n_slots
+  int32_t code_unmatched, pad_;
+  const void* code;
+};
+// what the host knows of such a step (api_routes.cpp fills it; kernels.h launch_star_groupby takes it)
+struct StarStep {
+  DevPlan flat;                            // the FLATTENED plan without the matched flag: inner column inner_col[j] is column nc + j
+  int32_t nc, n_inner, left, key_col, key_type, key_nullable;
+  int32_t inner_col[MI355Q_MAX_COLS], inner_type[MI355Q_MAX_COLS];  // plain types
+  const int8_t* inner_base[MI355Q_MAX_COLS];
+  int64_t inner_rows;
+  const int32_t* table;
+  int64_t key_min, n_slots;
+};
+
+// The two kernels' arguments from the step; false: not this member (the flattened route runs the step).
+inline bool make_star_args(const StarStep& st, const FragView& fv, int n_cus, uint32_t knob_flags, StarCodeArgs* code, StarArgs* out) {
+  StarArgs& a = *out;
+  StarCodeArgs& c = *code;
+  std::memset(&a, 0, sizeof(a));
+  std::memset(&c, 0, sizeof(c));
+  const DevPlan& p = st.flat;
+  const int nc = st.nc, nc2 = st.nc + st.n_inner;
+  if (p.desc_type != MI355Q_GROUP_BY_PERFECT_HASH || p.bf_active || p.n_group < 1 || p.n_group > kLdsKeys || fv.n_cols != nc ||
+      p.n_quals > MI355Q_MAX_QUALS || st.n_slots < 1 || st.n_slots > (int64_t)INT32_MAX || st.inner_rows < 0 || !st.table ||
+      (st.key_type != MI355Q_INT32 && st.key_type != MI355Q_INT64) || !all_aligned16(fv, st.key_col))
+    return false;
+  // the plan's quals: inner ones for the map, outer ones for the scan
+  DevPlan po = p;
+  po.n_quals = 0;
+  for (int i = 0; i < p.n_quals; ++i) {
+    const DevQual& q = p.quals[i];
+    if (q.col < nc) {
+      po.quals[po.n_quals++] = q;
+      continue;
+    }
+    if (q.col >= nc2 || !make_range_filter(q, &c.flt[c.n_flt], true)) return false;
+    c.flt_type[c.n_flt++] = q.type;
+  }
+  c.n_flt = merge_range_filters(c.flt, c.flt_type, c.n_flt);
+  for (int k = 0; k < c.n_flt; ++k) {
+    const int j = c.flt[k].col - nc;
+    if (st.inner_type[j] != c.flt_type[k]) return false;  // (plain columns: the qual's type is the storage type)
+    c.flt_base[k] = st.inner_base[j];
+  }
+  // the table side, as the family describes it — over a column table in which the inner columns are (aligned) nothings
+  std::vector<const void*> h2((size_t)std::max(fv.n_frags, 0) * nc2, nullptr);
+  for (int f = 0; f < fv.n_frags; ++f)
+    for (int k = 0; k < nc; ++k) h2[(size_t)f * nc2 + k] = fv.h_cols[(size_t)f * nc + k];
+  FragView fv2 = fv;
+  fv2.h_cols = h2.data();
+  fv2.n_cols = nc2;
+  bool need[kLdsVals][4] = {};
+  LdsArgs& l = a.l;
+  if (!lds_describe(po, fv2, 65536, knob_flags, &l, need, false)) return false;
+  if (l.baseline || l.bf_on || l.n_flt > kStarOuterFlt) return false;
+  for (int k = 0; k < l.n_flt; ++k)
+    if (l.flt[k].col >= nc) return false;
+  for (int v = 0; v < l.n_vals; ++v)
+    if (l.v[v].col >= nc) return false;
+  for (int g = 0; g < l.n_keys; ++g) {
+    const int j = l.key_col[g] - nc;
+    if (j < 0 || j >= st.n_inner || st.inner_type[j] != l.key_type[g]) return false;  // (every key an inner attribute, plain INT32 / INT64)
+    c.key_base[g] = st.inner_base[j];
+    c.key_type[g] = l.key_type[g];
+    c.key_translate[g] = l.key_translate[g];
+    c.key_min[g] = l.key_min[g];
+    c.key_card[g] = l.key_card[g];
+    c.key_mul[g] = l.key_mul[g];
+    c.key_null_key[g] = l.key_null_key[g];
+  }
+  // ONE window under the budget, as many replicas as fit
+  l.copy_bytes = lds_lay_out(l, need, l.entries);
+  if (l.copy_bytes > kLdsBudget) return false;
+  l.copies_lg = 0;
+  while (l.copies_lg < 6 && ((size_t)l.copy_bytes << (l.copies_lg + 1)) <= kLdsBudget) ++l.copies_lg;
+  if (fv.total_rows / (n_cus > 0 ? n_cus : 1) >= 0xfff00000ll) return false;  // (32-bit counters per workgroup, as make_lds_args)
+  // what a row without a dimension row gets
+  int32_t unmatched = kStarDrop;
+  if (st.left) {
+    bool pass = true;
+    for (int k = 0; k < c.n_flt; ++k) {  // (filter_pass on the column's NULL, on the host)
+      const RangeFilter& f = c.flt[k];
+      const int64_t x = int_null_of(c.flt_type[k]);
+      bool in = x >= f.lo && x <= f.hi;
+      if (f.negate) in = !in;
+      pass = pass && in && !(f.nullable && x == f.null_val);
+    }
+    int64_t idx = 0;
+    for (int g = 0; g < l.n_keys && pass; ++g) {
+      const int64_t d = l.key_null_key[g] - l.key_min[g];
+      if (!l.key_translate[g] || d < 0 || d >= l.key_card[g]) return false;  // (no entry for the NULL key: not this member's plan)
+      idx += d * l.key_mul[g];
+    }
+    if (pass && (idx < 0 || idx >= p.entry_count)) return false;
+    if (pass) unmatched = (int32_t)idx;
+  }
+  c.table = st.table;
+  c.n_slots = st.n_slots;
+  c.inner_rows = st.inner_rows;
+  c.n_keys = l.n_keys;
+  c.entry_count = p.entry_count;
+  c.code16 = p.entry_count <= 32767;
+  c.code_unmatched = unmatched;
+  a.key_col = st.key_col;
+  a.key_w8 = st.key_type == MI355Q_INT64;
+  a.key_nullable = st.key_nullable;
+  a.code16 = c.code16;
+  a.key_min = st.key_min;
+  a.n_slots = st.n_slots;
+  a.code_unmatched = unmatched;
+  return true;
+}
+inline int64_t star_map_bytes(const StarCodeArgs& c) { return (c.n_slots * (c.code16 ? 2 : 4) + 255) & ~(int64_t)255; }
 
 }  // namespace mq

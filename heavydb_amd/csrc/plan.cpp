@@ -493,9 +493,115 @@ int32_t qmd_init_projection(const mi355q_plan& p, const ResolvedTarget* ts, mi35
   return MI355Q_OK;
 }
 
+bool has_inner_refs(const mi355q_plan& p) {
+  for (int i = 0; i < p.n_quals && i < MI355Q_MAX_QUALS; ++i)
+    if (MI355Q_IS_INNER_COL(p.quals[i].col)) return true;
+  for (int g = 0; g < p.n_group_cols && g < MI355Q_MAX_GROUP_COLS; ++g)
+    if (MI355Q_IS_INNER_COL(p.group_cols[g])) return true;
+  return false;
+}
+
+int32_t flatten_inner_refs(const mi355q_plan& p, bool matched_flag, mi355q_plan* flat, InnerFlat* m) {
+  *m = InnerFlat{};
+  // (the counts are bounded before anything indexes inner_cols: a hostile n_inner_cols ends here)
+  if (p.n_cols < 0 || p.n_cols > MI355Q_MAX_COLS || p.n_inner_cols < 0 || p.n_inner_cols > MI355Q_MAX_COLS || p.n_quals < 0 ||
+      p.n_quals > MI355Q_MAX_QUALS || p.n_targets < 1 || p.n_targets > MI355Q_MAX_TARGETS || p.n_group_cols < 0 ||
+      p.n_group_cols > MI355Q_MAX_GROUP_COLS)
+    return MI355Q_ERR_INVALID_PLAN;
+  const bool refs = has_inner_refs(p);
+  if (p.join_outer_col < 0) return MI355Q_ERR_INVALID_PLAN;  // (an inner column needs the join)
+  if (refs) {
+    // the join keys are stated outer columns: the flattened plan has no join left to check them
+    const int n_keys = p.n_join_cols > 1 ? p.n_join_cols : 1;
+    if (n_keys > MI355Q_MAX_GROUP_COLS) return MI355Q_ERR_INVALID_PLAN;
+    for (int i = 0; i < n_keys; ++i) {
+      const int c = (i == 0 && p.n_join_cols <= 1) ? p.join_outer_col : p.join_outer_cols[i];
+      if (c < 0 || c >= p.n_cols) return MI355Q_ERR_INVALID_PLAN;
+    }
+    if (p.join_kind != MI355Q_JOIN_INNER && p.join_kind != MI355Q_JOIN_LEFT) return MI355Q_ERR_UNSUPPORTED;
+    if (p.n_exprs != 0) return MI355Q_ERR_UNSUPPORTED;
+    bool projection = true;
+    for (int t = 0; t < p.n_targets; ++t) projection = projection && p.targets[t].agg == MI355Q_PROJECT;
+    if (projection) return MI355Q_ERR_UNSUPPORTED;
+  }
+  const bool left = p.join_kind == MI355Q_JOIN_LEFT;
+  const int nc = p.n_cols;
+  *flat = p;
+  int32_t status = MI355Q_OK;
+  // inner column c as an outer column of the flattened plan: its index there, < 0 with `status` set when it has none
+  const auto outer_of = [&](int c) -> int {
+    if (c < 0 || c >= p.n_inner_cols) {
+      status = MI355Q_ERR_INVALID_PLAN;
+      return -1;
+    }
+    int j = 0;
+    while (j < m->n_inner && m->inner_col[j] != c) ++j;
+    if (j < m->n_inner) return nc + j;
+    const mi355q_col_desc& cd = p.inner_cols[c];
+    if (cd.encoding != MI355Q_ENC_NONE || (cd.logical_type != 0 && cd.logical_type != cd.type) ||
+        nc + m->n_inner + 1 + (matched_flag && !left ? 1 : 0) > MI355Q_MAX_COLS) {
+      status = MI355Q_ERR_UNSUPPORTED;
+      return -1;
+    }
+    m->inner_col[j] = c;
+    flat->cols[nc + j] = cd;
+    flat->col_ranges[nc + j] = p.inner_col_ranges[c];
+    if (left) {  // nullable under an outer join (resolve_targets' rule); the unmatched rows' NULL is a key of the range too
+      flat->cols[nc + j].nullable = 1;
+      if (refs) flat->col_ranges[nc + j].has_nulls = 1;
+    }
+    ++m->n_inner;
+    return nc + j;
+  };
+  for (int t = 0; t < p.n_targets; ++t) {
+    const mi355q_target& tg = p.targets[t];
+    if (tg.agg == MI355Q_PROJECT_KEY || tg.table == 0 || tg.col < 0) continue;
+    const int c = outer_of(tg.col);
+    if (c < 0) return status;
+    flat->targets[t].table = 0;
+    flat->targets[t].col = c;
+  }
+  for (int i = 0; i < p.n_quals; ++i) {
+    if (!MI355Q_IS_INNER_COL(p.quals[i].col)) continue;
+    const int c = outer_of(MI355Q_INNER_COL_INDEX(p.quals[i].col));
+    if (c < 0) return status;
+    flat->quals[i].col = c;
+  }
+  for (int g = 0; g < p.n_group_cols; ++g) {
+    if (!MI355Q_IS_INNER_COL(p.group_cols[g])) continue;
+    const int c = outer_of(MI355Q_INNER_COL_INDEX(p.group_cols[g]));
+    if (c < 0) return status;
+    flat->group_cols[g] = c;
+  }
+  flat->n_cols = nc + m->n_inner;
+  if (matched_flag && !left) {
+    if (p.n_quals >= MI355Q_MAX_QUALS || flat->n_cols >= MI355Q_MAX_COLS) return MI355Q_ERR_UNSUPPORTED;
+    m->flag_col = flat->n_cols++;
+    flat->cols[m->flag_col] = mi355q_col_desc{MI355Q_INT32, 0, MI355Q_ENC_NONE, 0};  // (INT32: the fast families' range filters read INT32 / INT64)
+    flat->col_ranges[m->flag_col] = mi355q_range{1, 0, 0, 1, 0.0, 0.0, 0};
+    mi355q_qual& mq = flat->quals[flat->n_quals++];
+    mq = mi355q_qual{};
+    mq.col = m->flag_col;
+    mq.op = MI355Q_EQ;
+    mq.ival = 1;
+  }
+  flat->join_outer_col = -1;
+  flat->join_table = nullptr;
+  flat->n_join_cols = 0;
+  flat->join_kind = MI355Q_JOIN_INNER;
+  flat->n_inner_cols = 0;
+  return MI355Q_OK;
+}
+
 int32_t qmd_init(const mi355q_plan& p, mi355q_qmd* q) {
   std::memset(q, 0, sizeof(*q));
   if (p.abi_version != MI355Q_ABI_VERSION) return MI355Q_ERR_INVALID_PLAN;
+  if (has_inner_refs(p)) {  // the layout of a plan with inner references is the layout of its flattened form
+    mi355q_plan fp;
+    InnerFlat m;
+    if (int32_t e = flatten_inner_refs(p, true, &fp, &m)) return e;
+    return qmd_init(fp, q);
+  }
   if (p.n_exprs != 0) {  // the layout of a plan with expressions is the layout of its lowered form
     mi355q_plan lp;
     if (int32_t e = lower_exprs(p, &lp, nullptr)) return e;

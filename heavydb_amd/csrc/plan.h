@@ -44,6 +44,20 @@ void layout_from_qmd(const mi355q_qmd& q, DevPlan* d);
 // as an INT32 column (its NULL becomes the INT32 NULL), so that the typed families, which filter on 4- and 8-byte
 // columns, take the lowered step
 int32_t lower_exprs(const mi355q_plan& p, mi355q_plan* lowered, DevExprSet* dev, bool widen_filter_bools = false);
+// Inner columns in a join step's quals and group columns (MI355Q_INNER_COL, include/mi355q.h): the ONE rewrite of such a
+// plan into its flattened, joinless form — inner column inner_col[k] becomes outer column n_cols + k, in order of first use
+// (targets, quals, group columns); matched_flag: under an INNER join one more INT32 column, flag_col, and the qual
+// `flag_col = 1` (a derived step over the joined rows of a one-to-many table needs neither).  A plan WITHOUT inner
+// references is rewritten the same way (the inner columns its targets read): execute_join_gather / _expand's derived plan;
+// its ranges stay the columns' own.  qmd_init, mi355q_explain, mi355q_reserve_workspace and execute_impl see inner
+// references only to hand them here (api_routes.cpp execute_inner_refs); no other code path meets one.
+struct InnerFlat {
+  int n_inner = 0;
+  int32_t inner_col[MI355Q_MAX_COLS] = {};
+  int flag_col = -1;
+};
+bool has_inner_refs(const mi355q_plan& p);
+int32_t flatten_inner_refs(const mi355q_plan& p, bool matched_flag, mi355q_plan* flat, InnerFlat* m);
 uint32_t expr_qual_mask(const mi355q_plan& p);  // expressions evaluated for every row (read by a qual, directly or through another)
 // one initialised row (key quads then slot init values); quad holds row_size / 8 entries
 void row_init_image(const mi355q_qmd& q, int64_t* quad);

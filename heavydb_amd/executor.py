@@ -58,9 +58,15 @@ class InputColDescriptor:
         return capi.ColDesc(self.type, int(self.nullable), self.encoding, self.logical_type)
 
 
+def inner(i: int) -> int:
+    """Names column i of inner_col_descs where a join step takes an outer column index: Qual.col and groupby_exprs
+    (capi.INNER_COL; `WHERE d.segment BETWEEN 2 AND 5 GROUP BY d.region` of fact JOIN dim)."""
+    return capi.INNER_COL(i)
+
+
 @dataclass
 class Qual:
-    """simple_quals entry: `col <op> literal`."""
+    """simple_quals entry: `col <op> literal`; `col` may be inner(i) in a join step."""
     col: int
     op: int
     literal: float | int = 0  # unused by IS_NULL / IS_NOT_NULL
@@ -230,6 +236,8 @@ class RelAlgExecutionUnit:
     def col_type(self, c: int) -> int:
         """storage type of outer column c; for a virtual column the expression's result type"""
         n = len(self.input_col_descs)
+        if capi.IS_INNER_COL(c):   # inner(i) in a qual of a join step: the dimension's column
+            return self.inner_col_descs[capi.INNER_COL_INDEX(c)].type
         return self.input_col_descs[c].type if c < n else self.exprs[c - n].result(self.input_col_descs, self.exprs[:c - n])[0]
 
     def to_plan(self) -> capi.Plan:

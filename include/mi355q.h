@@ -207,8 +207,32 @@ typedef struct mi355q_col_desc {
 #define MI355Q_QUAL_OR_GROUP(op) (((op) >> 8) & 0xff)
 #define MI355Q_QUAL_IN_OR_GROUP(op, g) ((op) | ((g) << 8))
 #define MI355Q_MAX_OR_GROUPS 3
+/* ---- inner (dimension) columns in a join step's WHERE and GROUP BY (star joins) ----
+ * `SELECT d.region, COUNT(*), SUM(f.amount) FROM fact f JOIN dim d ON f.did = d.id WHERE d.segment BETWEEN 2 AND 5 GROUP BY
+ * d.region`: in the reference quals and groupby_exprs are ColumnVars of any nesting level, and the join loop encloses the row
+ * function's body, so the dimension's columns are ordinary operands there.  Here MI355Q_INNER_COL(i) names column i of
+ * inner_cols[] wherever it is accepted: in quals[].col (members of OR groups included) and in group_cols[] (PROJECT_KEY targets
+ * follow the group column, as always).  It stays MI355Q_ERR_INVALID_PLAN in targets[].cond.col, in MI355Q_EX_COL arguments and
+ * in the join key columns; so does an inner reference of a plan without a join, or one whose index is >= n_inner_cols.
+ * MI355Q_ERR_UNSUPPORTED: a plan that has inner references and n_exprs > 0; a Projection step with an inner reference in a qual;
+ * an encoded inner column; a flattened plan (below) of more than MI355Q_MAX_COLS columns or MI355Q_MAX_QUALS quals.
+ *
+ * MEANING: exactly what the FLATTENED plan means over the joined rows.  The flattened plan has no join: every inner column the
+ * plan reads (quals, group columns, targets with `table` = 1) is one more outer column with the same mi355q_col_desc and range —
+ * under a LEFT join `nullable` becomes 1 and the range gets has_nulls — that holds, per joined row, the matched inner row's
+ * value, and the column's NULL for the unmatched row a LEFT join keeps.  An INNER join drops unmatched rows before any qual is
+ * evaluated (the flattened plan has an INT32 0 / 1 `matched` column as its last column and the qual `matched = 1` as its last
+ * qual); a one-to-many table yields one joined row per match.  So `d.attr = 3` is not TRUE for an unmatched LEFT row,
+ * `d.attr IS NULL` is TRUE for it, its group is the NULL key, and constrained_not_null applies as stated for the flattened
+ * plan.  mi355q_qmd_init of a plan with inner references returns, bit for bit, the descriptor of its flattened plan.
+ * mi355q_execute_async runs such a step to completion inside the call (the routes need the host between their passes), as it
+ * does for projected expressions; mi355q_wait then returns at once. */
+#define MI355Q_INNER_COL(i) ((int32_t)0x40000000 | (i))
+#define MI355Q_IS_INNER_COL(c) ((c) >= (int32_t)0x40000000)
+#define MI355Q_INNER_COL_INDEX(c) ((c) & 0x3fffffff)
+
 typedef struct mi355q_qual {
-  int32_t col; /* outer-table column index */
+  int32_t col; /* outer-table column index, or MI355Q_INNER_COL(inner-table column index) in the quals of a join step */
   int32_t op;  /* mi355q_op, + the disjunction it belongs to (MI355Q_QUAL_IN_OR_GROUP) */
   int64_t ival; /* literal for integer columns */
   double fval;  /* literal for double columns */
@@ -370,7 +394,8 @@ typedef struct mi355q_plan {
   int32_t n_group_cols; /* 0 = non-grouped aggregate; 1..MI355Q_MAX_GROUP_COLS group-by
                            columns: integers of any mix of widths, or DOUBLE / FLOAT
                            (floating-point keys always take the baseline layout; the key is the
-                           bit pattern of the value widened to double) */
+                           bit pattern of the value widened to double); in a join step a
+                           group column may be MI355Q_INNER_COL(i) */
   int32_t group_cols[MI355Q_MAX_GROUP_COLS];
 
   int32_t n_targets;
@@ -588,6 +613,11 @@ typedef struct mi355q_exec_options {
                                             update per joined row) even where the joined rows would be laid down as dense
                                             columns (k_join_expand) for a step without the join (tests and
                                             tools/join_expand_bench.py compare the two) */
+#define MI355Q_OPT_NO_STAR_GROUPBY 65536u /* star joins (MI355Q_INNER_COL): the flattened route (k_join_gather + the joinless
+                                            step) even where the star member would run — k_join_group_code maps every
+                                            join-table slot to its group's entry once, k_star_groupby_lds aggregates the fact
+                                            rows through that map with no temporary column (tests and tools/star_join_bench.py
+                                            compare the two) */
 
 /* per-call timing/selection report (what launchGpuCode logs,
  * QueryExecutionContext.cpp:334,364,579) */
@@ -598,7 +628,8 @@ typedef struct mi355q_exec_report {
   float total_ms;       /* HIP-event time of the whole call on the launch stream */
   int32_t n_launches;   /* launches of the dominant kernel */
   int32_t variant;      /* member of the family that ran (informational; e.g. k_groupby_lds: 4 run-time roles, 5 typed;
-                           k_groupby_lds_prog: 6 one LDS window, 7 several;
+                           k_groupby_lds_prog: 6 one LDS window, 7 several; k_star_groupby_lds: 8 / 9 the map's codes
+                           2 / 4 bytes wide;
                            k_idx_scatter: 6 plain records, 7 / 8 the packed 4- / 2-byte word; k_proj_compact: 0 the fast
                            member, 1 / 2 the general member and the one-to-many member without expressions, 16 the split
                            route, 32 / 33 the one-to-many member with expressions — evaluator in LDS / row at a time) */

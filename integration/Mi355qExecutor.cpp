@@ -58,10 +58,14 @@ struct Translator {
     emit_expr(e, x, [this](const Analyzer::ColumnVar* cv) { return find(outer_cols, cv->getColumnKey()); });
   }
 
-  // outer column index of a value expression: a plain column, or the virtual column of a projected expression
-  int value_col(const Analyzer::Expr* e) {
+  // outer column index of a value expression: a plain column, or the virtual column of a projected expression.
+  // inner_ok: the value stands where the plan takes MI355Q_INNER_COL — the operand of a qual, a group-by expression — so a
+  // column of the join's inner table (rte_idx 1: `WHERE d.segment BETWEEN 2 AND 5 GROUP BY d.region`) is named as such;
+  // inside an expression, a COUNT_IF / SUM_IF condition or an aggregate's argument it stays unsupported
+  int value_col(const Analyzer::Expr* e, bool inner_ok = false) {
     if (auto cv = dynamic_cast<const Analyzer::ColumnVar*>(e)) {
       if (cv->get_rte_idx() == 0) return find(outer_cols, cv->getColumnKey());
+      if (inner_ok && cv->get_rte_idx() == 1) return MI355Q_INNER_COL(find(inner_cols, cv->getColumnKey()));
       unsupported("inner column where an outer value is expected");
     }
     for (size_t k = 0; k < expr_of.size(); ++k)
@@ -148,14 +152,14 @@ mi355q_plan to_plan(const RelAlgExecutionUnit& ra, const std::vector<InputTableI
     if (!g) continue;
     if (p.n_group_cols >= MI355Q_MAX_GROUP_COLS) unsupported("too many group-by expressions");
     group_exprs.push_back(g.get());
-    p.group_cols[p.n_group_cols++] = t.value_col(g.get());
+    p.group_cols[p.n_group_cols++] = t.value_col(g.get(), /*inner_ok=*/true);
   }
   // simple_quals and quals: a conjunction
   int32_t n_or_groups = 0;
   std::vector<const Analyzer::Expr*> where;
   for (const auto* lst : {&ra.simple_quals, &ra.quals})
     for (const auto& q : *lst) where.push_back(q.get());
-  translate_where(where, [&t](const Analyzer::Expr* v) { return t.value_col(v); },
+  translate_where(where, [&t](const Analyzer::Expr* v) { return t.value_col(v, /*inner_ok=*/true); },
                   [&t](const ExprFiller& fill) { return t.new_bool_col(fill); }, p.quals, &p.n_quals, &n_or_groups);
   // A Projection (QueryDescriptionType::Projection): groupby_exprs is {nullptr} and no target is an aggregate — every target
   // is then a row-wise value (a column or an expression, TargetInfo.is_agg == false) and the step emits one entry per

@@ -40,6 +40,9 @@ PROJECT = 101  # a Projection step's non-aggregate target (the value of a column
 COUNT_IF, SUM_IF = 10, 11
 # mi355q_join_kind
 JOIN_INNER, JOIN_LEFT = 0, 1
+# a SEMI / ANTI level keeps a fact row once if the dimension has its key / if it has not (WHERE EXISTS / NOT EXISTS; a NULL key
+# matches nothing): the step means its joinless plan over those rows, the inner side is not readable (include/mi355q.h)
+JOIN_SEMI, JOIN_ANTI = 2, 3
 
 
 def INNER_COL(i: int) -> int:

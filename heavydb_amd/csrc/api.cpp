@@ -87,6 +87,7 @@ int32_t mq::api::attach_join(const mi355q_plan& p, const mi355q_inputs* in, DevP
   const mi355q_join_table* jt = p.join_table;
   const int n_keys = p.n_join_cols > 1 ? p.n_join_cols : 1;
   if (n_keys > MI355Q_MAX_GROUP_COLS || n_keys != jt->n_keys) return MI355Q_ERR_INVALID_PLAN;
+  // (SEMI / ANTI never get here as such: execute_exists_join hands over a carrier plan of kind INNER for the probe alone)
   if (p.join_kind != MI355Q_JOIN_INNER && p.join_kind != MI355Q_JOIN_LEFT) return MI355Q_ERR_UNSUPPORTED;
   for (int i = 0; i < n_keys; ++i) {
     const int c = (i == 0 && p.n_join_cols <= 1) ? p.join_outer_col : p.join_outer_cols[i];
@@ -834,6 +835,9 @@ int32_t mq::api::execute_impl(const mi355q_plan* plan, const mi355q_inputs* in,
   set_step_knobs(o);
   // ---- inner columns in the quals / group columns: the flattened plan's routes (the asynchronous call completes here)
   if (plan->abi_version == MI355Q_ABI_VERSION && has_inner_refs(*plan)) return execute_inner_refs(plan, in, o, out, report, reserved);
+  // ---- a SEMI / ANTI join level: the join as a row mask, then the joinless plan's routes (the asynchronous call completes here)
+  if (plan->abi_version == MI355Q_ABI_VERSION && is_exists_join(*plan))
+    return try_route(out, [&] { return execute_exists_join(plan, in, o, out, report, reserved); });
   const bool async = pend != nullptr;
   if (async) {
     TuneKnobs k = tune_knobs();

@@ -23,6 +23,7 @@ struct mi355q_join_table {
   int key_type = MI355Q_INT64;
   int n_keys = 1, width = 8;  // key components / component width of keyed tables
   int64_t entry_count = 0;
+  int64_t num_rows = 0;  // inner rows the table was built from (0: no slot holds a row)
   int64_t min_key = 0, max_key = 0;
   void* buf = nullptr;
   int64_t bytes = 0;
@@ -369,6 +370,11 @@ int32_t execute_join_expand(const mi355q_plan* plan, const mi355q_inputs* in, co
 // gather / expand routes above over the flattened plan; no other route meets an inner reference)
 int32_t execute_inner_refs(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
                            mi355q_exec_report* report, int64_t* reserved);
+// (a SEMI / ANTI join level, plan.h is_exists_join: asked directly behind the inner-reference check, and answers for good — the
+// join level becomes a row mask, k_join_exists_mask, and the joinless plan runs on `mask = 1`; no other route, no family and
+// not the row kernel meet these kinds, attach_join refuses them)
+int32_t execute_exists_join(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
+                            mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_perfect_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,
                              int n_cus, mi355q_result** out, mi355q_exec_report* report, int64_t* reserved);
 int32_t execute_affine_twin(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, const mi355q_qmd& q,

@@ -327,6 +327,7 @@ int32_t mi355q_join_build(const mi355q_join_spec* spec, void* stream, mi355q_joi
   } jg{jt};
   jt->device_id = spec->device_id;
   jt->key_type = spec->key_type;
+  jt->num_rows = spec->num_rows;
   const mi355q_range& r = spec->key_range;
   // PerfectJoinHashTable::getInstance (PerfectJoinHashTable.cpp:168-246): perfect when there is
   // ONE key column whose range is known and max-min+1 entries fit; else keyed

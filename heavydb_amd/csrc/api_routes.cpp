@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "api_internal.h"
@@ -69,7 +70,7 @@ struct PassLoop {
 
   // ---- laid out by prepare()
   int nc2 = 0;
-  int64_t pass_rows = 0, col_region = 0;
+  int64_t pass_rows = 0, col_region = 0, tab_bytes = 0, rows_bytes = 0;
   char* base = nullptr;
   const int8_t** d_tab = nullptr;
   char* after_tab = nullptr;
@@ -84,11 +85,10 @@ struct PassLoop {
   PassLoop(Workspace& ws_, int nc_, int n_extra_, const int32_t* width_, const mi355q_plan* derived_)
       : ws(ws_), nc(nc_), n_extra(n_extra_), width(width_), derived(derived_) {}
 
-  // sizes a pass from the free memory (o.pass_rows: the tests' override) and grows the workspace to hold it
-  int32_t prepare(const mi355q_inputs* in, const mi355q_exec_options& o, int64_t total_rows, int64_t max_frag_rows) {
+  // sizes a pass within `budget` bytes of temporary columns (o.pass_rows: the tests' override): the bytes the workspace must hold
+  int64_t lay_out(const mi355q_inputs* in, const mi355q_exec_options& o, int64_t total_rows, int64_t max_frag_rows, int64_t budget) {
     const int nf = in->n_frags;
     nc2 = nc + n_extra;
-    const int64_t budget = pass_budget(ws.bytes);
     int64_t row_bytes = 0;
     for (int k = 0; k < n_extra; ++k) row_bytes += width[k];
     int n_tmp = n_extra;
@@ -102,10 +102,15 @@ struct PassLoop {
     pass_rows = std::max<int64_t>(budget / std::max<int64_t>(row_bytes, 1), max_frag_rows);
     if (o.pass_rows > 0) pass_rows = std::max<int64_t>(o.pass_rows, max_frag_rows);  // tests: several passes
     if (pass_rows > total_rows) pass_rows = total_rows;
-    const int64_t tab_bytes = ((int64_t)sizeof(void*) * nf * (mask_column ? nc : nc2) + 255) & ~255ll;
-    const int64_t rows_bytes = ((int64_t)sizeof(int64_t) * nf + 255) & ~255ll;
+    tab_bytes = ((int64_t)sizeof(void*) * nf * (mask_column ? nc : nc2) + 255) & ~255ll;
+    rows_bytes = ((int64_t)sizeof(int64_t) * nf + 255) & ~255ll;
     col_region = ((pass_rows * row_bytes + pad * nf) + 255) & ~255ll;
-    const int64_t need = col_region + tab_bytes + bytes_after_tab + rows_bytes + 256 + bytes_after_err;
+    return col_region + tab_bytes + bytes_after_tab + rows_bytes + 256 + bytes_after_err;
+  }
+
+  // sizes a pass from the free memory and grows the workspace to hold it
+  int32_t prepare(const mi355q_inputs* in, const mi355q_exec_options& o, int64_t total_rows, int64_t max_frag_rows) {
+    const int64_t need = lay_out(in, o, total_rows, max_frag_rows, pass_budget(ws.bytes));
     if (const hipError_t he = ws.grow(need)) {
       if (alloc_failed != kNotTaken) last_hip_error = he;
       (void)hipGetLastError();
@@ -1889,6 +1894,143 @@ int32_t execute_masked(const mi355q_plan* plan, const mi355q_plan& rest, const B
         if (bfh.bf.any_raise) HIP_TRY(hipMemcpyAsync(&h_err, pl.d_err, sizeof(h_err), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return h_err;
+      }))
+    return e;
+  if (int32_t e = rs.finish_sync_if_timed(report, pl.acc, *plan, *in, total_rows)) return e;
+  *out = pl.res.release();
+  return MI355Q_OK;
+}
+
+// SEMI / ANTI join levels (MI355Q_JOIN_SEMI / _ANTI, include/mi355q.h: `WHERE EXISTS (SELECT 1 FROM d WHERE d.k = f.k)`, `NOT
+// EXISTS`, `IN (subquery)`).  Such a level reads no inner column: it is a row mask computed by probing the join table.  The
+// pre-pass k_join_exists_mask streams the key column(s) once and leaves one byte per row (1 = the row passes the level); the step
+// proper is the stated plan WITHOUT the join plus that INT8 column and the qual `mask = 1` (plan.cpp exists_join_plans), handed
+// to execute_impl — so every typed family, the Projection's members and the compiled-quals stage apply, over every kind of join
+// table.  Passes as execute_masked sizes them.  The pre-pass raises nothing.  Never kNotTaken.
+// (the one class restated as the INNER plan, below: from 100 M slots, and from the input size at which the INNER plan's family
+// is k_part_join, api.cpp select_family)
+constexpr int64_t kExistsAsInnerMinSlots = 100000000, kExistsAsInnerMinRows = (int64_t)64 << 20;
+int32_t execute_exists_join(const mi355q_plan* plan, const mi355q_inputs* in, const mi355q_exec_options& o, mi355q_result** out,
+                            mi355q_exec_report* report, int64_t* reserved) {
+  mi355q_plan jl, mp;
+  int mask_col = -1;
+  if (int32_t e = exists_join_plans(*plan, &jl, &mp, &mask_col)) return e;
+  const bool anti = plan->join_kind == MI355Q_JOIN_ANTI;
+  // the derived plan has the stated layout: the mask column is no key and no argument, and the quals stay — an `arg IS NOT NULL`
+  // qual on an aggregate's own argument, which is part of the layout (constrained_not_null), among them
+  mi355q_qmd q, q2;
+  if (int32_t e = qmd_init(jl, &q)) return e;
+  if (qmd_init(mp, &q2) != MI355Q_OK || std::memcmp(&q, &q2, sizeof(q)) != 0) return MI355Q_ERR_UNSUPPORTED;
+  for (int k = 0; k < plan->n_quals; ++k)
+    if (std::memcmp(&mp.quals[k], &plan->quals[k], sizeof(mi355q_qual)) != 0) return MI355Q_ERR_UNSUPPORTED;  // (cannot happen)
+  // the join as the device sees it: a carrier plan that keeps the stated columns and the join and nothing else (attach_join
+  // knows INNER and LEFT; the probe of an INNER level is the probe of these two)
+  mi355q_plan cp = *plan;
+  cp.n_quals = 0;
+  cp.n_group_cols = 0;
+  cp.n_targets = 1;
+  cp.targets[0] = mi355q_target{};
+  cp.targets[0].agg = MI355Q_COUNT;
+  cp.targets[0].col = -1;
+  cp.output_columnar_hint = MI355Q_OUTPUT_ROWWISE;
+  cp.scan_limit = 0;
+  cp.join_kind = MI355Q_JOIN_INNER;
+  cp.n_inner_cols = 0;
+  mi355q_qmd cq;
+  if (int32_t e = qmd_init(cp, &cq)) return e;
+  DevPlan d;
+  if (int32_t e = build_dev_plan(cp, cq, &d)) return e;
+  if (int32_t e = attach_join(cp, in, &d)) return e;
+  const int nc = plan->n_cols, nc2 = nc + 1, nf = in->n_frags;
+  int64_t total_rows = 0, max_frag_rows = 0;
+  if (int32_t e = frag_row_totals(*in, &total_rows, &max_frag_rows)) return e;
+  mi355q_inputs in_outer = *in;  // the derived steps have no inner side
+  in_outer.inner_col_buffers = nullptr;
+  in_outer.inner_num_rows = 0;
+  // an empty dimension (a table built from no row), or no fact row: no pre-pass.  SEMI: the joinless plan over no rows; ANTI:
+  // the joinless plan itself
+  if (plan->join_table->num_rows == 0 || total_rows == 0) {
+    if (reserved)
+      route_note(anti ? "anti join over an empty dimension (no k_join_exists_mask pre-pass): the joinless plan"
+                      : "semi join over an empty dimension (no k_join_exists_mask pre-pass): the joinless plan over no rows");
+    if (!anti) in_outer.n_frags = 0;
+    return execute_impl(&jl, &in_outer, &o, out, report, nullptr, reserved);
+  }
+  // SEMI over a ONE-TO-ONE table keeps exactly the rows the INNER join keeps (a row has at most one match).  Measured at 1 B rows
+  // (DESIGN 3.10): the non-grouped step over a 100 M-slot table — a 12.5 MB presence map, beyond one XCD's L2 — takes 7.3 ms as
+  // the INNER plan (k_part_scatter + k_part_join: the probes partitioned so that a map slice fits LDS) and 13.1 ms through the
+  // mask; with 1 M slots the mask route wins (6.7 against 7.4 ms), as it does for grouped steps at both sizes.  So that one
+  // class is restated, where the INNER plan's family is the measured one; a forced kernel_variant keeps the mask route.
+  if (!anti && o.kernel_variant == 0 && !o.force_generic && d.join_hash_type == 0 && q.desc_type == MI355Q_NON_GROUPED_AGGREGATE &&
+      d.join_entries >= kExistsAsInnerMinSlots && total_rows >= kExistsAsInnerMinRows) {
+    mi355q_plan ip = *plan;
+    ip.join_kind = MI355Q_JOIN_INNER;
+    mi355q_qmd iq;
+    DevPlan id;
+    FragView hv{nullptr, nullptr, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
+    if (qmd_init(ip, &iq) == MI355Q_OK && std::memcmp(&iq, &q, sizeof(q)) == 0 && build_dev_plan(ip, iq, &id) == MI355Q_OK &&
+        attach_join(ip, in, &id) == MI355Q_OK && join_part_supported(id, hv, cu_count_of(in->device_id))) {
+      if (reserved) route_note("semi join over a one-to-one table as the INNER join");
+      return execute_impl(&ip, in, &o, out, report, nullptr, reserved);
+    }
+  }
+  const int32_t mask_width = 1;
+  const int64_t mtab_bytes = ((int64_t)sizeof(void*) * nf + 255) & ~255ll;  // per fragment: its mask chunk
+  if (reserved) {  // mi355q_reserve_workspace / mi355q_explain: nothing is launched
+    {
+      FragView hv{nullptr, nullptr, in->col_buffers, in->num_rows, nf, nc, total_rows, max_frag_rows};
+      const std::string note = std::string(anti ? "anti" : "semi") + " join as a row mask: k_join_exists_mask" +
+                               (join_exists_mask_fast_eligible(d, hv) ? " (fast member)" : " (general member)");
+      route_note(note.c_str());
+    }
+    // the derived step's shape: the same fragments with nc2 columns (the pointers are looked at for alignment only)
+    std::vector<const void*> cols2((size_t)nf * nc2, nullptr);
+    for (int f = 0; f < nf; ++f) std::copy_n(in->col_buffers + (size_t)f * nc, nc, cols2.begin() + (size_t)f * nc2);
+    in_outer.col_buffers = cols2.data();
+    if (int32_t e = execute_impl(&mp, &in_outer, &o, out, report, nullptr, reserved)) return e;
+    // ... and the mask region of the passes, which the derived step knows nothing of: reported, and allocated when reserving
+    if (t_plan_only) {
+      PassLoop pl(ctx_of(in->device_id).maskws, nc, 1, &mask_width, &mp);
+      pl.mask_column = true;
+      pl.bytes_after_tab = mtab_bytes;
+      *reserved += pl.lay_out(in, o, total_rows, max_frag_rows, (int64_t)16 << 30);
+      return MI355Q_OK;
+    }
+    RouteScope rs(in->device_id, o.stream);
+    if (rs.status) return rs.status;
+    PassLoop pl(rs.ctx.maskws, nc, 1, &mask_width, &mp);
+    pl.mask_column = true;
+    pl.bytes_after_tab = mtab_bytes;
+    pl.alloc_failed = MI355Q_ERR_OUT_OF_GPU_MEM;
+    if (int32_t e = pl.prepare(in, o, total_rows, max_frag_rows)) return e;
+    *reserved += rs.ctx.maskws.bytes;
+    return MI355Q_OK;
+  }
+  RouteScope rs(in->device_id, o.stream);
+  if (rs.status) return rs.status;
+  const int n_cus = o.tune_cus > 0 ? std::min(o.tune_cus, cu_count_of(in->device_id)) : cu_count_of(in->device_id);
+  hipStream_t s = rs.s;
+  // one pass of fragments = as many as the mask region holds (1 B/row: 16 GB of it cover 16 G rows)
+  PassLoop pl(rs.ctx.maskws, nc, 1, &mask_width, &mp);
+  pl.mask_column = true;
+  pl.bytes_after_tab = mtab_bytes;
+  pl.alloc_failed = MI355Q_ERR_OUT_OF_GPU_MEM;
+  pl.clear_err_word = false;  // (the probe raises nothing)
+  if (int32_t e = pl.prepare(&in_outer, o, total_rows, max_frag_rows)) return e;
+  int8_t** d_mtab = (int8_t**)pl.after_tab;
+  std::vector<const void*> masks((size_t)nf);
+  if (int32_t e = pl.run(rs, &in_outer, o, report, [&](int f, int pnf) -> int32_t {
+        int64_t prows = 0, pmax = 0;
+        for (int i = 0; i < pnf; ++i) {
+          masks[(size_t)i] = pl.cols2[(size_t)i * nc2 + mask_col];
+          prows += in->num_rows[f + i];
+          pmax = std::max(pmax, in->num_rows[f + i]);
+        }
+        HIP_TRY(hipMemcpyAsync(d_mtab, masks.data(), sizeof(void*) * (size_t)pnf, hipMemcpyHostToDevice, s));
+        FragView fv{pl.d_tab, pl.d_rows + f, in->col_buffers + (size_t)f * nc, in->num_rows + f, pnf, nc, prows, pmax};
+        HIP_TRY(launch_join_exists_mask(d, anti, fv, d_mtab, n_cus, s));
+        HIP_TRY(hipStreamSynchronize(s));  // (masks / cols2 are re-used by the next pass)
+        return MI355Q_OK;
       }))
     return e;
   if (int32_t e = rs.finish_sync_if_timed(report, pl.acc, *plan, *in, total_rows)) return e;

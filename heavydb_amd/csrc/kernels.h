@@ -409,6 +409,25 @@ bool filter_mask_eligible(const BoolFilter& bf, const FragView& fv);
 hipError_t launch_filter_mask(const BoolFilter& bf, const BoolFilter* d_bf, const FragView& fv, int8_t* const* d_mask, int32_t* d_err,
                               int n_cus, hipStream_t s);
 
+// the row mask of a SEMI / ANTI join level (api_routes.cpp execute_exists_join): one byte per row, 1 = the row passes the level
+// (SEMI: its key has a match; ANTI: it has none; a NULL key matches nothing).  Chunks as filter_mask_chunk_bytes lays them out.
+// `p` carries the join alone (attach_join).  The fast member (kernels_filter.hip k_join_exists_mask_fast) takes ONE plain
+// INT32 / INT64 key in 16-byte aligned chunks over a perfect table (join_hash_type 0 / 2); the general member
+// (kernels_generic.hip k_join_exists_mask) takes everything else.
+struct JoinExistsArgs {
+  const int8_t* const* cols;  // [fragment][n_cols_table]
+  const int64_t* num_rows;
+  int8_t* const* mask;        // per fragment
+  int32_t n_frags, n_cols_table, key_col, key_nullable;
+  int64_t min_key, max_key;
+  const int32_t* table;       // one slot per key of [min_key, max_key]: the row id (one-to-one) / the payload offset (one-to-many), < 0 = no row
+  const uint32_t* bitmap;     // one-to-one tables: 1 bit per slot (or null: test the row id)
+};
+bool join_exists_mask_fast_eligible(const DevPlan& p, const FragView& fv);
+hipError_t launch_join_exists_mask(const DevPlan& p, bool anti, const FragView& fv, int8_t* const* d_mask, int n_cus, hipStream_t s);
+hipError_t launch_join_exists_mask_general(const DevPlan& p, bool anti, const FragView& fv, int8_t* const* d_mask, int n_cus,
+                                           hipStream_t s);
+
 // non-grouped aggregates whose arguments are two-register programs (regprog.h AggProgArgs: up to 4 arguments over up to 4
 // operand columns) with range quals on up to 4 plain INT32 / INT64 / INT8 columns, evaluated in the scan's registers
 // (kernels_filter.hip k_scan_agg_prog).  `p`: the plan over the lowered columns — its quals, targets and init values.  An

@@ -3,6 +3,8 @@
 //   k_scan_agg_prog                    non-grouped aggregates whose ARGUMENTS are programs: SUM(a * b) WHERE c < k in one pass
 // (the Projection family evaluates its typed expression targets itself, kernels_proj.hip).  Both run the programs on the
 // four rows of a quad together, on values already in registers, with no stack, no scratch and no node decode per row.
+// And the other producer of such a row mask, which runs no program: k_join_exists_mask_fast, the join level of a SEMI / ANTI
+// step (one plain key column probed in a perfect join table; behind the filter mask's launcher).
 //
 // ---- the row mask
 // The reference compiles a WHERE clause into the row function (Executor::compileBody, NativeCodegen.cpp:3455; arithmetic
@@ -891,6 +893,151 @@ bool filter_mask_eligible(const BoolFilter& bf, const FragView& fv) {
     if (!all_aligned16(fv, bf.col[k])) return false;
   }
   return true;
+}
+
+// =========================================================================== the join level of a SEMI / ANTI step as a row mask
+// k_join_exists_mask_fast (api_routes.cpp execute_exists_join; the general member is kernels_generic.hip k_join_exists_mask):
+// ONE plain INT32 / INT64 key column in 16-byte aligned chunks over a PERFECT join table.  The streaming skeleton of
+// fast_common.h scan_fragments: a workgroup walks tiles of kBlock x kJxUQ quads, every lane loads its kJxUQ key quads
+// (16-byte non-temporal loads) before it looks at the first key, then issues the probes of all its rows — cached loads, the
+// table is what should stay in L2 — before it looks at the first answer, and a quad's four result bytes leave as ONE 4-byte
+// store (a wave writes 256 contiguous bytes).  The probe of a row: the NULL and range tests, slot = key - min_key, then
+//   BITS — a one-to-one table with its presence bitmap: the slot's bit (1/32 of the row-id table: 12.5 MB for 100 M slots, not 400 MB);
+//   else the slot's word >= 0: the row id of a one-to-one table without a bitmap, offsets[slot] of a one-to-many table (one test).
+// A NULL key and a key outside [min_key, max_key] never touch the table (jx_probe).  ANTI: the inverted byte.  The quads behind a
+// fragment's last full tile go one per lane; its last, partial quad goes row by row with BYTE stores: nothing is written
+// behind a fragment's last row (the chunk the pass loop carves is padded to a multiple of 16 bytes all the same — the
+// consuming families load the mask as one 4-byte word per quad — and those bytes are never looked at).
+// No barrier, no LDS, no atomics.
+namespace {
+
+constexpr int kJxUQ = 2;
+
+template <bool K64>
+MQ_D bool jx_in_range(const JoinExistsArgs& a, int64_t k) {
+  constexpr int64_t kNull = K64 ? INT64_MIN : (int64_t)INT32_MIN;
+  return k >= a.min_key && k <= a.max_key && !(a.key_nullable && k == kNull);
+}
+// what the table says of the row's slot, as a word whose top bit is CLEAR when the slot holds a row; -1 for a row that is not `in`
+// (NULL key, key outside the range).  The load itself is unconditional — a row that is not `in` reads a word of the row-count
+// array instead, never the table — so that a lane's probes are all in flight before the first answer is looked at (behind a
+// branch per row the compiler waits for every probe in turn: eight dependent round trips per lane and tile).
+template <bool BITS>
+MQ_D int32_t jx_probe(const JoinExistsArgs& a, bool in, int64_t off) {
+  const int32_t* const idle = (const int32_t*)a.num_rows;
+  int32_t w;
+  if (BITS) {
+    const int32_t* p = in ? (const int32_t*)(a.bitmap + (off >> 5)) : idle;
+    w = (int32_t)(~(uint32_t)*(const MQ_GLOBAL int32_t*)p << (31 - (int)(off & 31)));
+  } else {
+    const int32_t* p = in ? a.table + off : idle;
+    w = *(const MQ_GLOBAL int32_t*)p;
+  }
+  return in ? w : -1;
+}
+
+template <bool K64, bool BITS, bool ANTI>
+__global__ __launch_bounds__(kBlock) void k_join_exists_mask_fast(JoinExistsArgs a) {
+  using KT = typename std::conditional<K64, int64_t, int32_t>::type;
+  const int64_t tile_q = (int64_t)kBlock * kJxUQ;
+  const int64_t gtid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t gsize = (int64_t)gridDim.x * kBlock;
+  for (int f = 0; f < a.n_frags; ++f) {
+    const int8_t* kb = a.cols[(size_t)f * a.n_cols_table + a.key_col];
+    int8_t* const out = a.mask[f];
+    const int64_t n = a.num_rows[f];
+    const int64_t nq = n >> 2;
+    const int64_t n_tiles = nq / tile_q;
+    for (int64_t t = (blockIdx.x + (int64_t)f * 7) % gridDim.x; t < n_tiles; t += gridDim.x) {
+      const int64_t q0 = t * tile_q + threadIdx.x;
+      Quad<KT> kq[kJxUQ];
+#pragma unroll
+      for (int u = 0; u < kJxUQ; ++u) load_quad<KT>(kb, q0 + (int64_t)u * kBlock, kq[u]);
+      int32_t ans[kJxUQ][4];
+#pragma unroll
+      for (int u = 0; u < kJxUQ; ++u) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int64_t k = (int64_t)kq[u].v[i];
+          ans[u][i] = jx_probe<BITS>(a, jx_in_range<K64>(a, k), k - a.min_key);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kJxUQ; ++u) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w |= (uint32_t)((ans[u][i] >= 0) != ANTI) << (8 * i);
+        __builtin_nontemporal_store(w, (MQ_GLOBAL uint32_t*)out + q0 + (int64_t)u * kBlock);
+      }
+    }
+    // ragged end of the fragment: whole quads past the last full tile, then < 4 rows (byte stores)
+    for (int64_t q = n_tiles * tile_q + gtid; q < nq; q += gsize) {
+      Quad<KT> k0;
+      load_quad<KT>(kb, q, k0);
+      int32_t ans[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t k = (int64_t)k0.v[i];
+        ans[i] = jx_probe<BITS>(a, jx_in_range<K64>(a, k), k - a.min_key);
+      }
+      uint32_t w = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w |= (uint32_t)((ans[i] >= 0) != ANTI) << (8 * i);
+      __builtin_nontemporal_store(w, (MQ_GLOBAL uint32_t*)out + q);
+    }
+    const int64_t tail = (nq << 2) + gtid;
+    if (tail < n) {
+      const int64_t k = (int64_t)load_one<KT>(kb, tail);
+      const int32_t ans = jx_probe<BITS>(a, jx_in_range<K64>(a, k), k - a.min_key);
+      out[tail] = (int8_t)((ans >= 0) != ANTI);
+    }
+  }
+}
+
+template <bool K64, bool BITS>
+void jx_launch(bool anti, int64_t grid, const JoinExistsArgs& a, hipStream_t s) {
+  if (anti) hipLaunchKernelGGL((k_join_exists_mask_fast<K64, BITS, true>), dim3((unsigned)grid), dim3(kBlock), 0, s, a);
+  else hipLaunchKernelGGL((k_join_exists_mask_fast<K64, BITS, false>), dim3((unsigned)grid), dim3(kBlock), 0, s, a);
+}
+
+}  // namespace
+
+bool join_exists_mask_fast_eligible(const DevPlan& p, const FragView& fv) {
+  if (tune_knobs().flags & MI355Q_OPT_LDS_GENERIC_MEMBER) return false;  // (the A/B switch of the typed members: the general one)
+  if (p.join_n_keys != 1 || (p.join_hash_type != 0 && p.join_hash_type != 2) || !p.join_buf) return false;
+  if (p.join_type != MI355Q_INT32 && p.join_type != MI355Q_INT64) return false;  // plain, unencoded
+  if (p.join_max < p.join_min || p.join_entries != p.join_max - p.join_min + 1) return false;
+  return all_aligned16(fv, p.join_col);
+}
+
+hipError_t launch_join_exists_mask(const DevPlan& p, bool anti, const FragView& fv, int8_t* const* d_mask, int n_cus, hipStream_t s) {
+  if (fv.n_frags <= 0 || fv.max_frag_rows <= 0) return hipSuccess;
+  if (!join_exists_mask_fast_eligible(p, fv)) return launch_join_exists_mask_general(p, anti, fv, d_mask, n_cus, s);
+  JoinExistsArgs a{};
+  a.cols = fv.d_cols;
+  a.num_rows = fv.d_num_rows;
+  a.mask = d_mask;
+  a.n_frags = fv.n_frags;
+  a.n_cols_table = fv.n_cols;
+  a.key_col = p.join_col;
+  a.key_nullable = p.join_nullable ? 1 : 0;
+  a.min_key = p.join_min;
+  a.max_key = p.join_max;
+  a.table = (const int32_t*)p.join_buf;  // (one-to-many: the offsets lead the buffer)
+  a.bitmap = p.join_hash_type == 0 ? p.join_bitmap : nullptr;
+  const bool bits = a.bitmap != nullptr;
+  // 4 workgroups per CU: a row's probe is a dependent random read behind its key, and more waves hide more of them
+  const int bpc = tune_knobs().blocks_per_cu > 0 ? tune_knobs().blocks_per_cu : 4;
+  const int64_t want = fv.max_frag_rows / 4 / (kBlock * kJxUQ) + 1;
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)n_cus * bpc, want));
+  if (p.join_type == MI355Q_INT64) {
+    if (bits) jx_launch<true, true>(anti, grid, a, s);
+    else jx_launch<true, false>(anti, grid, a, s);
+  } else {
+    if (bits) jx_launch<false, true>(anti, grid, a, s);
+    else jx_launch<false, false>(anti, grid, a, s);
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_filter_mask(const BoolFilter& bf, const BoolFilter* d_bf, const FragView& fv, int8_t* const* d_mask, int32_t* d_err,

@@ -950,6 +950,32 @@ __global__ __launch_bounds__(kBlock) void k_join_gather(DevPlan p, JoinGather jg
   }
 }
 
+// ---- the join level of a SEMI / ANTI step as a row mask (api_routes.cpp execute_exists_join), general member: keyed tables,
+// composite keys, encoded or narrow key columns, unaligned chunks.  Per row: the key's components, the NULL test (a NULL
+// component matches nothing, hash_join_idx_nullable), the probe, one byte: 1 = the row passes the level (`anti`: the
+// inverted byte).  `cols`: the n_cols_table STATED columns of every fragment.  Barrier-free like k_join_gather.
+__global__ __launch_bounds__(kBlock) void k_join_exists_mask(DevPlan p, int anti, int n_cols_table, const int8_t* const* __restrict__ cols,
+                                                              const int64_t* __restrict__ num_rows, int8_t* const* __restrict__ mask,
+                                                              int n_frags) {
+  const int64_t gtid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t gsize = (int64_t)gridDim.x * kBlock;
+  for (int f = 0; f < n_frags; ++f) {
+    const int8_t* const* fc = cols + (size_t)f * n_cols_table;
+    const int64_t n = num_rows[f];
+    int8_t* const out = mask[f];
+    for (int64_t pos = gtid; pos < n; pos += gsize) {
+      int64_t jk[MI355Q_MAX_GROUP_COLS];
+      bool null_key = false;
+      for (int i = 0; i < p.join_n_keys; ++i) {
+        jk[i] = decode_int(fc[p.join_cols[i]], p.join_types[i], pos);
+        null_key = null_key || (p.join_nullables[i] && jk[i] == int_null_of(p.join_types[i]));
+      }
+      const bool hit = !null_key && join_lookup(p, jk).count > 0;
+      out[pos] = (int8_t)(hit != (anti != 0));
+    }
+  }
+}
+
 // ---- projected expressions of ONE operation over ONE plain column, four rows per lane -------------------------
 // k_project interprets a node list per row, one 4- or 8-byte load and store per lane, and its by-value expression
 // set is indexed with run-time values (so it lives in scratch): 1.4 TB/s on `CAST(x AS DOUBLE)` — 8.7 ms of the
@@ -1858,6 +1884,14 @@ hipError_t launch_join_gather(const DevPlan& p, int n_inner, const int32_t* inne
     jg.null_pat[j] = null_pat[j];
   }
   hipLaunchKernelGGL(k_join_gather, dim3(grid_for(max_frag_rows, n_cus * 8)), dim3(kBlock), 0, s, p, jg, d_cols, d_num_rows, n_frags);
+  return hipGetLastError();
+}
+
+hipError_t launch_join_exists_mask_general(const DevPlan& p, bool anti, const FragView& fv, int8_t* const* d_mask, int n_cus,
+                                           hipStream_t s) {
+  if (fv.n_frags <= 0 || fv.max_frag_rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_join_exists_mask, dim3(grid_for(fv.max_frag_rows, n_cus * 8)), dim3(kBlock), 0, s, p, anti ? 1 : 0, fv.n_cols,
+                     fv.d_cols, fv.d_num_rows, d_mask, fv.n_frags);
   return hipGetLastError();
 }
 

@@ -518,6 +518,7 @@ int32_t flatten_inner_refs(const mi355q_plan& p, bool matched_flag, mi355q_plan*
       const int c = (i == 0 && p.n_join_cols <= 1) ? p.join_outer_col : p.join_outer_cols[i];
       if (c < 0 || c >= p.n_cols) return MI355Q_ERR_INVALID_PLAN;
     }
+    if (is_exists_join(p)) return MI355Q_ERR_INVALID_PLAN;  // (the inner side of a SEMI / ANTI level is not readable)
     if (p.join_kind != MI355Q_JOIN_INNER && p.join_kind != MI355Q_JOIN_LEFT) return MI355Q_ERR_UNSUPPORTED;
     if (p.n_exprs != 0) return MI355Q_ERR_UNSUPPORTED;
     bool projection = true;
@@ -593,6 +594,50 @@ int32_t flatten_inner_refs(const mi355q_plan& p, bool matched_flag, mi355q_plan*
   return MI355Q_OK;
 }
 
+bool is_exists_join(const mi355q_plan& p) {
+  return p.join_outer_col >= 0 && (p.join_kind == MI355Q_JOIN_SEMI || p.join_kind == MI355Q_JOIN_ANTI);
+}
+
+int32_t exists_join_plans(const mi355q_plan& p, mi355q_plan* joinless, mi355q_plan* masked, int* mask_col) {
+  // (the counts are bounded before anything is indexed with them)
+  if (p.n_cols < 0 || p.n_cols > MI355Q_MAX_COLS || p.n_inner_cols < 0 || p.n_inner_cols > MI355Q_MAX_COLS || p.n_quals < 0 ||
+      p.n_quals > MI355Q_MAX_QUALS || p.n_targets < 1 || p.n_targets > MI355Q_MAX_TARGETS || p.n_group_cols < 0 ||
+      p.n_group_cols > MI355Q_MAX_GROUP_COLS)
+    return MI355Q_ERR_INVALID_PLAN;
+  if (!is_exists_join(p) || !p.join_table) return MI355Q_ERR_INVALID_PLAN;
+  // the join keys are stated outer columns: the derived plans have no join left to check them
+  const int n_keys = p.n_join_cols > 1 ? p.n_join_cols : 1;
+  if (n_keys > MI355Q_MAX_GROUP_COLS) return MI355Q_ERR_INVALID_PLAN;
+  for (int i = 0; i < n_keys; ++i) {
+    const int c = (i == 0 && p.n_join_cols <= 1) ? p.join_outer_col : p.join_outer_cols[i];
+    if (c < 0 || c >= p.n_cols) return MI355Q_ERR_INVALID_PLAN;
+  }
+  // the inner side of these kinds is not readable
+  if (has_inner_refs(p)) return MI355Q_ERR_INVALID_PLAN;
+  for (int t = 0; t < p.n_targets; ++t)
+    if (p.targets[t].table != 0) return MI355Q_ERR_INVALID_PLAN;
+  // (the reference evaluates a qual's expressions inside the join loop: mi355q.h)
+  if (p.n_exprs != 0) return MI355Q_ERR_UNSUPPORTED;
+  if (p.n_cols >= MI355Q_MAX_COLS || p.n_quals >= MI355Q_MAX_QUALS) return MI355Q_ERR_UNSUPPORTED;  // no room for the mask / its qual
+  *joinless = p;
+  joinless->join_outer_col = -1;
+  joinless->join_table = nullptr;
+  joinless->n_join_cols = 0;
+  joinless->join_kind = MI355Q_JOIN_INNER;
+  joinless->n_inner_cols = 0;
+  *masked = *joinless;
+  const int mc = masked->n_cols++;
+  masked->cols[mc] = mi355q_col_desc{MI355Q_INT8, 0, MI355Q_ENC_NONE, 0};
+  masked->col_ranges[mc] = mi355q_range{1, 0, 0, 1, 0.0, 0.0, 0};
+  mi355q_qual& mq = masked->quals[masked->n_quals++];
+  mq = mi355q_qual{};
+  mq.col = mc;
+  mq.op = MI355Q_EQ;
+  mq.ival = 1;
+  *mask_col = mc;
+  return MI355Q_OK;
+}
+
 int32_t qmd_init(const mi355q_plan& p, mi355q_qmd* q) {
   std::memset(q, 0, sizeof(*q));
   if (p.abi_version != MI355Q_ABI_VERSION) return MI355Q_ERR_INVALID_PLAN;
@@ -601,6 +646,12 @@ int32_t qmd_init(const mi355q_plan& p, mi355q_qmd* q) {
     InnerFlat m;
     if (int32_t e = flatten_inner_refs(p, true, &fp, &m)) return e;
     return qmd_init(fp, q);
+  }
+  if (is_exists_join(p)) {  // the layout of a SEMI / ANTI step is the layout of its joinless plan
+    mi355q_plan jl, mp;
+    int mask_col;
+    if (int32_t e = exists_join_plans(p, &jl, &mp, &mask_col)) return e;
+    return qmd_init(jl, q);
   }
   if (p.n_exprs != 0) {  // the layout of a plan with expressions is the layout of its lowered form
     mi355q_plan lp;

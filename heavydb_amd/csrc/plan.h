@@ -58,6 +58,13 @@ struct InnerFlat {
 };
 bool has_inner_refs(const mi355q_plan& p);
 int32_t flatten_inner_refs(const mi355q_plan& p, bool matched_flag, mi355q_plan* flat, InnerFlat* m);
+// SEMI / ANTI join levels (MI355Q_JOIN_SEMI / _ANTI, include/mi355q.h): the ONE rewrite of such a plan.  `joinless` is the stated
+// plan without the join — what the step means over the rows that pass the join level, and whose descriptor qmd_init returns;
+// `masked` is joinless plus one INT8 NOT NULL column in [0, 1] behind the stated ones (mask_col) and the qual `mask_col = 1` as
+// the last qual — what api_routes.cpp execute_exists_join runs once k_join_exists_mask has written that column.  The refusals
+// are the ones mi355q.h states.
+bool is_exists_join(const mi355q_plan& p);
+int32_t exists_join_plans(const mi355q_plan& p, mi355q_plan* joinless, mi355q_plan* masked, int* mask_col);
 uint32_t expr_qual_mask(const mi355q_plan& p);  // expressions evaluated for every row (read by a qual, directly or through another)
 // one initialised row (key quads then slot init values); quad holds row_size / 8 entries
 void row_init_image(const mi355q_qmd& q, int64_t* quad);

@@ -220,7 +220,7 @@ class RelAlgExecutionUnit:
     inner_col_descs: List[InputColDescriptor] = field(default_factory=list)
     join_outer_col: int | Sequence[int] = -1   # one column, or a list for a composite key
     join_table: Optional["HashJoin"] = None
-    join_kind: int = 0                          # capi.JOIN_INNER / JOIN_LEFT
+    join_kind: int = 0                          # capi.JOIN_INNER / JOIN_LEFT / JOIN_SEMI / JOIN_ANTI (the last two read no inner column)
     # ExecutionOptions / globals shaping the layout
     max_groups_buffer_entry_guess: int = 16384  # Execute.cpp:111
     bigint_count: bool = False

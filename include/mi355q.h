@@ -160,8 +160,36 @@ typedef enum mi355q_agg {
 
 /* join kinds: INNER drops outer rows without a match; LEFT keeps them once with every inner
  * column NULL (JoinType::LEFT; Executor::buildJoinLoops, IRCodegen.cpp, JoinLoop kinds
- * UpperBound/Set/Singleton with an outer-join "found" flag) */
-typedef enum mi355q_join_kind { MI355Q_JOIN_INNER = 0, MI355Q_JOIN_LEFT = 1 } mi355q_join_kind;
+ * UpperBound/Set/Singleton with an outer-join "found" flag).
+ *
+ * SEMI and ANTI are the join levels the reference plans for `WHERE EXISTS (SELECT .. FROM d WHERE d.k = f.k)` /
+ * `f.k IN (SELECT k FROM d)` and for `WHERE NOT EXISTS (..)`.  The values follow the reference's JoinType (Shared/sqldefs.h:
+ * INNER, LEFT, SEMI, ANTI in that order — stated from memory: the reference tree was not at hand when this was written, so no
+ * line is cited; the binding maps the enumerators by name, not by value).
+ *   - A row passes the join level of a SEMI step when its key has at least one match in the join table, and then counts ONCE,
+ *     however many inner rows match: SEMI over a one-to-many table is not the INNER join, whose row counts once per match.
+ *   - A row passes an ANTI level when its key has no match.
+ *   - A NULL key (a nullable key column holding its type's sentinel; any NULL component of a composite key) matches nothing,
+ *     as hash_join_idx_nullable has it everywhere else in this library: it fails SEMI and passes ANTI.  That is NOT EXISTS,
+ *     not the three-valued NOT IN (under which a NULL key — or a NULL among the dimension's keys — keeps no row).
+ *   - The step means its JOINLESS plan over the rows that pass: the same targets, quals, group columns and layout.
+ *     mi355q_qmd_init of a SEMI / ANTI plan returns, bit for bit, the descriptor of the same plan with the join removed
+ *     (join_outer_col = -1, no join table, n_inner_cols = 0).  Every kind of table mi355q_join_build makes is accepted
+ *     (perfect or keyed, one-to-one or one-to-many, composite keys).
+ *   - The inner side of these kinds is not readable: a target with table = 1, an MI355Q_INNER_COL reference in a qual or a
+ *     group column, or a missing join table is MI355Q_ERR_INVALID_PLAN.
+ *   - MI355Q_ERR_UNSUPPORTED together with n_exprs > 0: the reference evaluates a qual's expressions inside the join loop,
+ *     so a row the join level drops must raise nothing, and the row mask this library turns the join level into, beside
+ *     the lowered plan, does not state that.  Left for a later step.  Also MI355Q_ERR_UNSUPPORTED: a plan that already has
+ *     MI355Q_MAX_COLS columns or MI355Q_MAX_QUALS quals (the mask and its qual need one of each).
+ *   mi355q_qmd_init, mi355q_explain, mi355q_reserve_workspace, mi355q_execute and mi355q_execute_async answer alike for a
+ *   refused plan; mi355q_execute_async completes a SEMI / ANTI step inside the call. */
+typedef enum mi355q_join_kind {
+  MI355Q_JOIN_INNER = 0,
+  MI355Q_JOIN_LEFT = 1,
+  MI355Q_JOIN_SEMI = 2,
+  MI355Q_JOIN_ANTI = 3
+} mi355q_join_kind;
 
 /* QueryDescriptionType (enums.h:53-59) */
 typedef enum mi355q_desc_type {

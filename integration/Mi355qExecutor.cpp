@@ -221,7 +221,15 @@ mi355q_plan to_plan(const RelAlgExecutionUnit& ra, const std::vector<InputTableI
     }
     p.join_outer_col = p.join_outer_cols[0];
     p.n_join_cols = n > 1 ? n : 0;
-    p.join_kind = jc.type == JoinType::LEFT ? MI355Q_JOIN_LEFT : MI355Q_JOIN_INNER;
+    // by name, never by value — and a kind the library does not know is refused, not run as an INNER join (a SEMI level over
+    // a table with duplicate keys would count a fact row once per match)
+    switch (jc.type) {
+      case JoinType::INNER: p.join_kind = MI355Q_JOIN_INNER; break;
+      case JoinType::LEFT: p.join_kind = MI355Q_JOIN_LEFT; break;
+      case JoinType::SEMI: p.join_kind = MI355Q_JOIN_SEMI; break;
+      case JoinType::ANTI: p.join_kind = MI355Q_JOIN_ANTI; break;
+      default: unsupported("join type");
+    }
   }
   p.join_table = join_table;
   p.max_groups_buffer_entry_guess = (int64_t)max_groups_buffer_entry_guess;

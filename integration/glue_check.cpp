@@ -604,6 +604,64 @@ int main() {
         expect(same7, "one-to-many projection differs from the oracle's");
         expect(live7 > 0 && pairs > 0, "every matching outer row shows its two inner rows");
         std::printf("  %lld entries, %lld outer rows with both of their matches\n", (long long)live7, (long long)pairs);
+        // -------------------------------------------------------- query 8: a SEMI level over the same ONE-TO-MANY table
+        //   a fact row counts ONCE however many rows of d2 carry its key (the INNER join of query 7 shows it twice)
+        {
+          std::printf("query 8: SELECT COUNT(*), SUM(t.key) FROM t WHERE EXISTS (SELECT 1 FROM d2 WHERE d2.k = t.fk)\n");
+          RelAlgExecutionUnit ra8;
+          ra8.input_col_descs.push_back(std::make_shared<const InputColDescriptor>(4, kTable, kDb, 0));
+          ra8.input_col_descs.push_back(std::make_shared<const InputColDescriptor>(0, kTable, kDb, 0));
+          JoinCondition jc8;
+          jc8.type = JoinType::SEMI;
+          jc8.quals.push_back(std::make_shared<Analyzer::BinOper>(SQLTypeInfo(kBOOLEAN, true), kEQ, fk, dk));
+          ra8.join_quals.push_back(jc8);
+          ra8.groupby_exprs.push_back(nullptr);
+          Analyzer::AggExpr cnt8(SQLTypeInfo(kBIGINT, true), kCOUNT, nullptr), sum8(SQLTypeInfo(kBIGINT, false), kSUM, v);
+          ra8.target_exprs = {&cnt8, &sum8};
+          mi355q_plan h8{};
+          h8.abi_version = MI355Q_ABI_VERSION;
+          h8.n_cols = 2;
+          h8.cols[0] = {MI355Q_INT64, 0, 0, 0};
+          h8.cols[1] = {MI355Q_INT64, 0, 0, 0};
+          h8.col_ranges[0] = {1, 0, -50, M + 49, 0, 0, 0};
+          h8.col_ranges[1] = {1, 0, 7, key_max, 0, 0, 0};
+          h8.n_targets = 2;
+          h8.targets[0] = {MI355Q_COUNT, -1, 0, 0, {}};
+          h8.targets[1] = {MI355Q_SUM, 1, 0, 0, {}};
+          h8.join_outer_col = 0;
+          h8.join_outer_cols[0] = 0;
+          h8.join_kind = MI355Q_JOIN_SEMI;
+          h8.max_groups_buffer_entry_guess = 16384;
+          h8.num_tuples = N + M;
+          const mi355q_plan p8 = mi355q_glue::to_plan(ra8, qi2, &executor, jt2, 16384, false);
+          compare_plans(h8, p8);
+          expect(p8.join_kind == MI355Q_JOIN_SEMI, "a SEMI level stays a SEMI level");
+          h8.join_table = jt2;
+          mi355q_qmd q8;
+          MQCK(mi355q_qmd_init(&h8, &q8));
+          std::vector<int64_t> fr8_rows;
+          const FetchResult fr8 = fetch(t, {4, 0}, &fr8_rows);
+          const ResultSetPtr rs8 = mi355q_glue::run_query_mi355q(ra8, fr8, qi2, qmd_of(q8), &executor, 0, 16384, jt2, {}, M);
+          expect(q8.desc_type == MI355Q_NON_GROUPED_AGGREGATE, "layout");
+          // the reference, here: the dimension's keys as a set
+          std::vector<char> present((size_t)(M / 2), 0);
+          for (int64_t i = 0; i < M; ++i) present[(size_t)k2[(size_t)i]] = 1;
+          const int64_t* tfk = (const int64_t*)t.cols[4].host.data();
+          const int64_t* tkey = (const int64_t*)t.cols[0].host.data();
+          int64_t want_cnt = 0, want_sum = 0, inner_cnt = 0;
+          std::vector<int32_t> per_key((size_t)(M / 2), 0);
+          for (int64_t i = 0; i < M; ++i) ++per_key[(size_t)k2[(size_t)i]];
+          for (int64_t r = 0; r < N; ++r) {
+            if (tfk[r] < 0 || tfk[r] >= M / 2 || !present[(size_t)tfk[r]]) continue;
+            ++want_cnt;
+            want_sum += tkey[r];
+            inner_cnt += per_key[(size_t)tfk[r]];
+          }
+          const int64_t* got8 = (const int64_t*)const_cast<ResultSetStorage*>(rs8->getStorage())->getUnderlyingBuffer();
+          expect(got8[0] == want_cnt && got8[1] == want_sum, "SEMI join differs from the rows whose key the dimension has");
+          expect(want_cnt > 0 && want_cnt < N && inner_cnt > want_cnt, "the INNER join over this table would count more rows");
+          std::printf("  COUNT(*) = %lld (the INNER join: %lld), SUM(t.key) = %lld\n", (long long)got8[0], (long long)inner_cnt, (long long)got8[1]);
+        }
         executor.column_ranges[{kDim, 0}] = ExpressionRange::makeIntRange(0, M - 1, 0, false);
         mi355q_join_free(jt2);
         orc_join_free(oj2);

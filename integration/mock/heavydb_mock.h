@@ -40,7 +40,7 @@ enum EncodingType { kENCODING_NONE = 0, kENCODING_FIXED = 1, kENCODING_RL = 2, k
 enum SQLOps { kEQ = 0, kBW_EQ, kNE, kLT, kGT, kLE, kGE, kAND, kOR, kNOT, kMINUS, kPLUS, kMULTIPLY, kDIVIDE, kMODULO, kUMINUS, kISNULL, kISNOTNULL, kEXISTS, kCAST };
 enum SQLAgg { kAVG = 0, kMIN, kMAX, kSUM, kCOUNT, kAPPROX_COUNT_DISTINCT, kAPPROX_QUANTILE, kSAMPLE, kSINGLE_VALUE, kMODE,
               kCOUNT_IF, kSUM_IF, kINVALID_AGG };
-enum class JoinType { INNER, LEFT };
+enum class JoinType { INNER, LEFT, SEMI, ANTI };
 enum class ExecutorDeviceType { CPU, GPU };
 
 class SQLTypeInfo {

@@ -1182,16 +1182,30 @@ MQ_D uint64_t gcd_u64(uint64_t a, uint64_t b) {
   return a;
 }
 // (two stages without barriers or shuffles: one partial per lane, then 256 lanes fold 256 partials each; the host folds the rest)
+constexpr int kGcdKeys = 8;  // keys a lane has in flight
 __global__ __launch_bounds__(kBlock) void k_key_gcd(const int8_t* __restrict__ col, int width, int64_t n, int64_t kmin, int nullable,
                                                      unsigned long long* __restrict__ per_lane) {
   uint64_t g = 0;
   const int64_t null_v = width == 4 ? (int64_t)INT32_MIN : INT64_MIN;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-    const int64_t v = width == 4 ? (int64_t)((const int32_t*)col)[i] : ((const int64_t*)col)[i];
-    if (nullable && v == null_v) continue;
-    const uint64_t d = (uint64_t)v - (uint64_t)kmin;
-    if (d == 0) continue;
-    g = g == 0 ? d : (d % g == 0 ? g : gcd_u64(g, d));
+  // A lane folds the keys i0, i0 + step, ... in that order; it fetches kGcdKeys of them with independent loads before it
+  // folds any, because the data-dependent gcd loop would otherwise keep one load in flight per lane.
+  const int64_t step = (int64_t)gridDim.x * kBlock;
+  for (int64_t i0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; i0 < n; i0 += step * kGcdKeys) {
+    int64_t v[kGcdKeys];
+#pragma unroll
+    for (int k = 0; k < kGcdKeys; ++k) {
+      const int64_t i = i0 + k * step;
+      const int64_t at = i < n ? i : i0;  // clamped: always loadable
+      v[k] = width == 4 ? (int64_t)((const int32_t*)col)[at] : ((const int64_t*)col)[at];
+      if (i >= n) v[k] = kmin;  // past the end: folds as the minimum does, not at all
+    }
+#pragma unroll
+    for (int k = 0; k < kGcdKeys; ++k) {
+      if (nullable && v[k] == null_v) continue;
+      const uint64_t d = (uint64_t)v[k] - (uint64_t)kmin;
+      if (d == 0) continue;
+      g = g == 0 ? d : (d % g == 0 ? g : gcd_u64(g, d));
+    }
   }
   per_lane[(size_t)blockIdx.x * kBlock + threadIdx.x] = g;
 }

@@ -779,19 +779,6 @@ MQ_D bool is_count_op(int op) { return op == SO_COUNT || op == SO_COUNT_NN; }
 MQ_D int64_t lds_slot_value(int op, const char* base, uint32_t e) {
   return is_count_op(op) ? (int64_t)((const uint32_t*)base)[e] : ((const int64_t*)base)[e];
 }
-MQ_D void global_merge(int op, int64_t* gslot, int64_t partial) {
-  switch (op) {
-    case SO_COUNT:
-    case SO_COUNT_NN:
-    case SO_SUM_I: atomicAdd((unsigned long long*)gslot, (unsigned long long)partial); break;
-    case SO_SUM_F: atomicAdd((double*)gslot, bits_dbl(partial)); break;
-    case SO_MIN_I: atomicMin((long long*)gslot, (long long)partial); break;
-    case SO_MAX_I: atomicMax((long long*)gslot, (long long)partial); break;
-    case SO_MIN_F: a_minmax_f64<true, false, false>(gslot, bits_dbl(partial), 0.0); break;
-    case SO_MAX_F: a_minmax_f64<true, true, false>(gslot, bits_dbl(partial), 0.0); break;
-    default: break;
-  }
-}
 
 constexpr uint32_t kNoEntry = 0xffffffffu;
 
@@ -1185,7 +1172,50 @@ __global__ __launch_bounds__(kPartBlock) void k_part_aggregate(PartGeom g, const
 }
 
 // ------------------------------------------------------------------------- phase 3
-// merge one partial row (internal slots) into the output table with the reference's insert-or-find
+// one output slot's merge of a partial on the table (other lanes may merge into the same row): the reference's agg_* and
+// agg_*_skip_val forms
+MQ_D void merge_slot(int op, bool null_init, int64_t init, int64_t* s, int64_t v) {
+  if (!null_init) {
+    switch (op) {
+      case SO_COUNT:
+      case SO_COUNT_NN:
+      case SO_SUM_I: a_sum_i64<true>(s, v); break;
+      case SO_SUM_F: a_sum_f64<true>(s, bits_dbl(v)); break;
+      case SO_MIN_I: a_min_i64<true>(s, v); break;
+      case SO_MAX_I: a_max_i64<true>(s, v); break;
+      case SO_MIN_F: a_minmax_f64<true, false, false>(s, bits_dbl(v), 0.0); break;
+      case SO_MAX_F: a_minmax_f64<true, true, false>(s, bits_dbl(v), 0.0); break;
+      default: break;
+    }
+    return;
+  }
+  switch (op) {  // slot starts at the NULL sentinel: first value overwrites it
+    case SO_SUM_I: a_sum_i64_skip<true>(s, v, init); break;
+    case SO_SUM_F: a_sum_f64_skip<true>(s, bits_dbl(v), bits_dbl(init)); break;
+    case SO_MIN_I: a_min_i64_skip<true>(s, v, init); break;
+    case SO_MAX_I: a_max_i64_skip<true>(s, v, init); break;
+    case SO_MIN_F: a_minmax_f64<true, false, true>(s, bits_dbl(v), bits_dbl(init)); break;
+    case SO_MAX_F: a_minmax_f64<true, true, true>(s, bits_dbl(v), bits_dbl(init)); break;
+    default: break;
+  }
+}
+// (the partial holds no value: a null_init slot keeps what it has, NULL or not)
+MQ_D bool partial_has_no_value(const PartSlots& ps, const int64_t* part) { return ps.nn_slot >= 0 && part[ps.nn_slot] == 0; }
+
+// merge one partial row (internal slots) into the row of the output table that holds `key`
+MQ_D void merge_partial_row(const PartSlots& ps, const TableArgs& tab, int64_t key, int64_t* slots, const int64_t* part) {
+  const bool no_value = partial_has_no_value(ps, part);
+  for (int j = 0; j < tab.sp.n; ++j) {
+    const int m = ps.out_map[j];
+    if (m < 0) {
+      if (tab.sp.op[j] == SO_KEY) MQ_STORE64(slots + j, key);
+      continue;
+    }
+    if (tab.sp.null_init[j] && no_value) continue;
+    merge_slot(tab.sp.op[j], tab.sp.null_init[j], tab.init[j], slots + j, part[m]);
+  }
+}
+// ... with the reference's insert-or-find
 MQ_D void merge_partial_global(const PartSlots& ps, const TableArgs& tab, const SpillList& sl, int64_t key,
                                const int64_t* part) {
   int64_t* slots = baseline_find_or_insert(tab.out, tab.entry_count, tab.row_quad, 8, key);
@@ -1193,27 +1223,76 @@ MQ_D void merge_partial_global(const PartSlots& ps, const TableArgs& tab, const 
     atomicCAS(sl.d_err, 0, -1);  // out of group slots: the caller resizes and retries
     return;
   }
-  const bool no_value = ps.nn_slot >= 0 && part[ps.nn_slot] == 0;
+  merge_partial_row(ps, tab, key, slots, part);
+}
+// partial (op) partial, as values
+MQ_D int64_t fold_partial(int op, int64_t a, int64_t b) {
+  switch (op) {
+    case SO_COUNT:
+    case SO_COUNT_NN:
+    case SO_SUM_I: return (int64_t)((uint64_t)a + (uint64_t)b);
+    case SO_SUM_F: return dbl_bits(bits_dbl(a) + bits_dbl(b));
+    case SO_MIN_I: return b < a ? b : a;
+    case SO_MAX_I: return b > a ? b : a;
+    case SO_MIN_F: return bits_dbl(b) < bits_dbl(a) ? b : a;
+    case SO_MAX_F: return bits_dbl(b) > bits_dbl(a) ? b : a;
+    default: return a;
+  }
+}
+// What merge_partial_row leaves in output slot j of a row that still holds its initial values, as a value: merge_slot
+// without the memory.  Not null_init: the atomic's own fold of init[j] and the partial (an add, a min or a max: 0.0 + -0.0
+// is +0.0 there too).  null_init, the _skip forms on a slot that holds the sentinel: a partial equal to the sentinel is
+// skipped and any other replaces it — the integer forms compare bits, so the partial is what the slot holds either way;
+// the double forms compare values.  false: the merge does not touch the slot.
+MQ_D bool merged_on_init(const PartSlots& ps, const TableArgs& tab, int j, int64_t key, bool no_value, const int64_t* part,
+                         int64_t* out) {
+  const int m = ps.out_map[j];
+  const int op = tab.sp.op[j];
+  if (m < 0) {
+    *out = key;
+    return op == SO_KEY;
+  }
+  const int64_t init = tab.init[j], v = part[m];
+  if (!tab.sp.null_init[j]) {
+    *out = fold_partial(op, init, v);
+    return true;
+  }
+  if (no_value) return false;
+  const bool fp = op == SO_SUM_F || op == SO_MIN_F || op == SO_MAX_F;
+  const bool known = fp || op == SO_SUM_I || op == SO_MIN_I || op == SO_MAX_I;  // (merge_slot leaves any other op alone)
+  *out = fp && bits_dbl(v) == bits_dbl(init) ? init : v;
+  return known;
+}
+
+// k_lattice_emit's row when its own CAS put the key into an EMPTY slot.  The row then holds the initial values of the member's
+// launch_init_buffer; one lane works on a lattice point and distinct points have distinct keys, so no other lane of the
+// launch finds this key; every k_spill_merge precedes the launch on the stream and no other kernel writes the table
+// meanwhile: the row is this lane's alone.  What the merge would leave in it is stored, two slots at a time where the
+// address allows.  (Not for k_spill_merge: several of its entries can carry one key.)
+MQ_D void store_fresh_row(const PartSlots& ps, const TableArgs& tab, int64_t key, int64_t* slots, const int64_t* part) {
+  const bool no_value = partial_has_no_value(ps, part);
+  bool held = false;  // slot j - 1 is 16-byte aligned and waits for slot j to leave with it
+  int64_t hv = 0;
   for (int j = 0; j < tab.sp.n; ++j) {
-    const int m = ps.out_map[j];
-    if (m < 0) {
-      if (tab.sp.op[j] == SO_KEY) MQ_STORE64(slots + j, key);
-      continue;
-    }
-    if (!tab.sp.null_init[j]) {
-      global_merge(tab.sp.op[j], slots + j, part[m]);
-      continue;
-    }
-    if (no_value) continue;  // the partial holds no value: the slot keeps what it has (NULL or not)
-    const int64_t v = part[m];
-    switch (tab.sp.op[j]) {  // slot starts at the NULL sentinel: first value overwrites it
-      case SO_SUM_I: a_sum_i64_skip<true>(slots + j, v, tab.init[j]); break;
-      case SO_SUM_F: a_sum_f64_skip<true>(slots + j, bits_dbl(v), bits_dbl(tab.init[j])); break;
-      case SO_MIN_I: a_min_i64_skip<true>(slots + j, v, tab.init[j]); break;
-      case SO_MAX_I: a_max_i64_skip<true>(slots + j, v, tab.init[j]); break;
-      case SO_MIN_F: a_minmax_f64<true, false, true>(slots + j, bits_dbl(v), bits_dbl(tab.init[j])); break;
-      case SO_MAX_F: a_minmax_f64<true, true, true>(slots + j, bits_dbl(v), bits_dbl(tab.init[j])); break;
-      default: break;
+    int64_t v = 0;
+    const bool stored = merged_on_init(ps, tab, j, key, no_value, part, &v);
+    if (held) {
+      held = false;
+      if (stored) {
+        v2i64_t w;
+        w.x = hv;
+        w.y = v;
+        *(v2i64_t*)(slots + j - 1) = w;
+      } else {
+        slots[j - 1] = hv;
+      }
+    } else if (stored) {
+      if (((uintptr_t)(slots + j) & 15) == 0 && j + 1 < tab.sp.n) {
+        held = true;
+        hv = v;
+      } else {
+        slots[j] = v;
+      }
     }
   }
 }
@@ -1288,19 +1367,6 @@ __global__ __launch_bounds__(256) void k_spill_merge(PartSlots ps, TableArgs tab
 // accumulator (`acc`: ns_int 8-byte partials per lattice point, row p x E + e, zeroed at the start of the step; counts
 // widen to 64 bits there; COUNT(*) == 0 marks a point no row has reached).  One workgroup owns a unit and the chunks'
 // launches follow each other on the stream, so those rows are updated with plain loads and stores.
-MQ_D int64_t fold_partial(int op, int64_t a, int64_t b) {
-  switch (op) {
-    case SO_COUNT:
-    case SO_COUNT_NN:
-    case SO_SUM_I: return (int64_t)((uint64_t)a + (uint64_t)b);
-    case SO_SUM_F: return dbl_bits(bits_dbl(a) + bits_dbl(b));
-    case SO_MIN_I: return b < a ? b : a;
-    case SO_MAX_I: return b > a ? b : a;
-    case SO_MIN_F: return bits_dbl(b) < bits_dbl(a) ? b : a;
-    case SO_MAX_F: return bits_dbl(b) > bits_dbl(a) ? b : a;
-    default: return a;
-  }
-}
 MQ_D int count_slot_of(const PartSlots& ps, int ns) {
   int cs = 0;
   for (int m = 0; m < ns; ++m)
@@ -1406,7 +1472,8 @@ __global__ __launch_bounds__(kPartBlock) void k_part_aggregate_idx(PartGeom g, c
 }
 
 // after the last chunk: every point some row has reached leaves for the output table under its real key, through the
-// reference's insert-or-find — a row the heavy-hitter / full-run spill path of an earlier chunk created is merged into
+// reference's insert-or-find — a row the heavy-hitter / full-run spill path of an earlier chunk created is merged into, a row
+// the insert made is stored (store_fresh_row)
 __global__ __launch_bounds__(256) void k_lattice_emit(PartGeom g, PartSlots ps, TableArgs tab, SpillList sl,
                                                       const int64_t* __restrict__ acc, int64_t kmin, uint64_t stride,
                                                       uint64_t card) {
@@ -1422,7 +1489,12 @@ __global__ __launch_bounds__(256) void k_lattice_emit(PartGeom g, PartSlots ps, 
     if (idx >= card) continue;
     int64_t part[kMaxInt];
     for (int m = 0; m < kMaxInt; ++m) part[m] = m < ns ? row[m] : 0;
-    merge_partial_global(ps, tab, sl, (int64_t)((uint64_t)kmin + idx * stride), part);
+    const int64_t key = (int64_t)((uint64_t)kmin + idx * stride);
+    bool fresh;
+    int64_t* slots = baseline_find_or_insert_fresh(tab.out, tab.entry_count, tab.row_quad, key, &fresh);
+    if (!slots) atomicCAS(sl.d_err, 0, -1);  // out of group slots: the caller resizes and retries
+    else if (fresh) store_fresh_row(ps, tab, key, slots, part);
+    else merge_partial_row(ps, tab, key, slots, part);  // a spill merge made the row: it holds a partial
   }
 }
 

@@ -388,6 +388,29 @@ MQ_FN int64_t* baseline_find_or_insert(int64_t* buf, uint32_t entry_count, int r
   } while (hp != h);
   return nullptr;
 }
+// The same insert-or-find for 8-byte keys — hash, probe order and the nullptr of a full table — that also says who made the
+// row: *fresh is true when this call's CAS found the slot EMPTY (the caller inserted the key), false when the key was there.
+// (One exit from the loop: with the early returns of the function above and the out-parameter, hipcc 7.2 crashes in
+// SimplifyCFG when this is inlined into k_lattice_emit.)
+MQ_FN int64_t* baseline_find_or_insert_fresh(int64_t* buf, uint32_t entry_count, int row_quad, int64_t key, bool* fresh) {
+  const uint32_t h = murmur3_u64((uint64_t)key) % entry_count;
+  uint32_t hp = h;
+  int64_t* slots = nullptr;
+  bool made = false;
+  for (;;) {
+    int64_t* row = buf + (size_t)hp * row_quad;
+    const int64_t old = (int64_t)MQ_CAS64(row, kEmptyKey64, key);
+    if (old == kEmptyKey64 || old == key) {
+      slots = row + 1;
+      made = old == kEmptyKey64;
+      break;
+    }
+    hp = hp + 1 == entry_count ? 0 : hp + 1;
+    if (hp == h) break;
+  }
+  *fresh = made;
+  return slots;
+}
 
 // Multi-column keys (key_count components of key_width bytes each, packed at the row start).
 // The reference's GPU build claims the first component with a CAS and lets late arrivals spin
